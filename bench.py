@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Benchmark: device-resident receive-path transform (checksum + parse + demux) on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W          (N > 1: launched by torch.distributed.run)
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+                                                           (N > 1: launched by torch.distributed.run)
 
 A step = one dk_rx_process pass over one HBM-resident batch of the workload (default: BASELINE config 2,
 1,048,576 x 1500 B IPv4/TCP frames over 1,024 flows, 1 % corrupted tail), plus, for N > 1, the RCCL all-reduce of the
@@ -9,8 +10,11 @@ per-flow packet counts (dk_rx_flow_counts_allreduce over a dk_comm.h communicato
 every --gather-every batches on the launch stream). Weak scaling: every rank owns one batch (its packet
 shard).
 `value` = sum of frame bytes processed by all ranks / max-over-ranks time.  Rank 0 prints one JSON line.
-At N = 1 the line also carries the other BASELINE configs as extras (C3 64 B UDP, C4 IMIX shard, C5 10k-flow shard
-kernel-only and end to end from pinned host memory, C1-shaped CPU baseline), each with its own roofline fields.
+A plain run sets up, warms up, times the K steps and prints the line; --dump-outputs DIR also writes what the last
+timed step computed (the result arrays and the accumulated counters) as DIR/<name>.npy.
+With --full the line also carries the measured streaming-read ceiling and, at N = 1, the CPU baselines and the other
+BASELINE configs as extras (C3 64 B UDP, C4 IMIX shard, C5 10k-flow shard kernel-only and end to end from pinned host
+memory, C1-shaped CPU baseline), each with its own roofline fields (--no-cpu / --no-extras leave those parts out).
 """
 from __future__ import annotations
 
@@ -202,6 +206,31 @@ def mbuf_zero_copy_rate(dev, stream, n=1 << 17, slot=2048, data_off=128, reps=5)
             "data_off": data_off, "delivered_frac": round(float(np.mean((got["meta"] & 0xFF) == 0)), 3),
             "stat": "median", "reps": reps,
             "pipeline": "dk_rx_process on a host-mapped (page-locked) blob: zero-copy, PCIe-bound"}
+
+
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs writes at most this much in all
+DUMP_SEED = 20240607
+
+
+def dump_outputs(path, res, sr):
+    """--dump-outputs: what the timed path's caller holds after the last timed step, as float64 .npy files (every u32
+    and every counter here is exact in a float64): the per-frame result arrays the last step wrote and the flow /
+    verdict counters accumulated over the warmup and timed steps. When the per-frame arrays would pass DUMP_MAX_BYTES,
+    the same fixed, seeded sample of frames is taken from each (its indices in frame_index.npy)."""
+    os.makedirs(path, exist_ok=True)
+    got = res.to_numpy()
+    fc, vc = sr.counts()
+    counts = {"flow_counts": fc.cpu().numpy().view(np.uint64), "verdict_counts": vc.cpu().numpy().view(np.uint64)}
+    frame = {k: v for k, v in got.items() if k not in counts}
+    budget = DUMP_MAX_BYTES - 8 * sum(v.size for v in counts.values())
+    keep = budget // (8 * (len(frame) + 1))  # frames per array, frame_index included
+    idx = np.arange(res.n, dtype=np.int64)
+    if res.n > keep:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(res.n, size=keep, replace=False))
+        frame = {k: v[idx] for k, v in frame.items()}
+    frame["frame_index"] = idx
+    for k, v in {**frame, **counts}.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(v, dtype=np.float64))
 
 
 def cpu_info():
@@ -620,9 +649,15 @@ def main():
     ap.add_argument("--workload", default="c2_tcp1500", choices=sorted(k for k in WORKLOADS if k != "c1_tcp1078"))
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--cpu-sample", type=int, default=1 << 17)
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the streaming-read ceiling, the CPU baselines and the "
+                         "other BASELINE configs (the extras of the line); a plain run only times --workload")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step computed (result arrays, accumulated counters) to "
+                         "DIR/<name>.npy (rank 0, float64, at most 64 MB: a fixed seeded sample of frames beyond that)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baselines")
     ap.add_argument("--host-frames", type=int, default=1 << 19)
-    ap.add_argument("--no-extras", action="store_true")
+    ap.add_argument("--no-extras", action="store_true", help="--full without the read ceiling and the other configs")
     ap.add_argument("--preheat-seconds", type=float, default=PREHEAT_S,
                     help="untimed receive launches before each measurement's warmup steps (GPU clock ramp)")
     ap.add_argument("--backend", default="gloo", choices=["nccl", "gloo"],
@@ -639,6 +674,9 @@ def main():
     ap.add_argument("--counts-out", default="",
                     help="write the node-wide flow / verdict counters after the timed steps to this .npz (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    extras, cpu = args.full and not args.no_extras, args.full and not args.no_cpu
     set_preheat(args.preheat_seconds)
     GATHER_EVERY = max(args.gather_every, 1)
 
@@ -697,6 +735,8 @@ def main():
         fc, vc = sr.counts()
         np.savez(args.counts_out, flow_counts=fc.cpu().numpy().view(np.uint64),
                  verdict_counts=vc.cpu().numpy().view(np.uint64), steps=args.steps + args.warmup)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res, sr)
     mine = {"rank": rank, "kernel_ms_per_step": round(kern_avg * 1e3, 4),
             "wall_ms_per_step": round(wall / args.steps * 1e3, 4), "frames": batch.n, "frame_bytes": frame_bytes,
             "gpu": device_identity(dev)}
@@ -744,13 +784,13 @@ def main():
                      "kernel_ms_avg": round(kern_avg * 1e3, 4),
                      "algorithmic_bytes_per_launch": algo, "kernel": rx_kernel_name(int(batch.frames_bytes), batch.n)},
     }
-    if not args.no_extras:
+    if extras:
         ceil_gbs, ceil_cfg = read_ceiling(batch, stream)
         out["roofline"]["measured_read_ceiling"] = {"value": round(ceil_gbs, 1), "unit": "GB/s", "probe": ceil_cfg,
                                                     "frac": round(achieved / ceil_gbs, 4)}
     out.update(scale_fields(world, comm, per_rank, coll, GATHER_EVERY))
     host = cpu_info()
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if rank == 0 and world == 1 and cpu:
         blob_s, off_s, lens_s = host_sample(batch, args.cpu_sample)
         r = cpu_rate(blob_s, off_s, lens_s, flows, args.cpu_seconds)
         out["cpu_baseline"] = {"value": round(r["gbps"], 3), "unit": "GB/s", "cores": 1, "kind": "port",
@@ -759,7 +799,7 @@ def main():
                                          f"{r['reps']} reps over >= {args.cpu_seconds:.0f} s, median; "
                                          f"oracle/dk_oracle.cpp (C++ restatement of the Rust path, clang -O3, 1 thread "
                                          f"as the reference's single-threaded LibOS)", **host}
-        if not args.no_extras:
+        if extras:
             # the reference's own config 1 shape (tcp-echo: 1 KiB payloads on one 4-tuple to port 12345,
             # tools/ci/job/linux.py:145, examples/tcp-echo/client.rs:82) and config 3 (64 B UDP), 1 core each
             e1 = RxEngine(Config(synth.BOB_IPV4), device=dev)
@@ -784,7 +824,7 @@ def main():
             rm = cpu_rate(blob_s, off_s, lens_s, flows, max(args.cpu_seconds / 2, 1.0), threads=threads)
             out["cpu_baseline_all_cores"] = {"value": round(rm["gbps"], 3), "unit": "GB/s", "cores": rm["cores"],
                                              "mpkt_s": round(rm["mpkt_s"], 2), **host}
-    if rank == 0 and world == 1 and not args.no_extras and name == "c2_tcp1500":
+    if rank == 0 and world == 1 and extras and name == "c2_tcp1500":
         # the other BASELINE configs on this GPU (per-GPU shards of C4 / C5), each with its own roofline
         c3, e, _, _ = rx_extra("c3_udp64", dev, stream, steps=40, warmup=4, rotate=8)
         c3b, e, _, _ = rx_extra("c3_udp64", dev, stream, steps=40, warmup=4, rotate=8, dst_ip=False)

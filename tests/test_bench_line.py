@@ -58,3 +58,66 @@ def test_missized_communicator_is_refused():
             bench.scale_fields(world, FakeRccl(nranks), rows(world), [0.008], 8)
         assert e.value.code == 4
     bench.check_comm_size(2, 2)  # the right size passes
+
+
+class FakeReceiver:  # stands in for shard.ShardedReceiver after drain(): counts() gives the accumulated counters
+    def __init__(self, res):
+        self.res = res
+
+    def counts(self):
+        return self.res.t["flow_counts"], self.res.t["verdict_counts"]
+
+
+def _results(n, nflows, seed):
+    import numpy as np
+    import torch
+
+    from demikernel_amd import RxResults
+
+    res = RxResults(n, nflows)
+    rng = np.random.default_rng(seed)
+    for k, v in res.t.items():  # every bit pattern, the top bit included: u32 / u64 storage seen through int32 / int64
+        hi = 2 ** 32 if v.dtype == torch.int32 else 2 ** 53
+        a = rng.integers(0, hi, v.numel(), dtype=np.uint64)
+        v.copy_(torch.from_numpy(a.astype(np.uint32).view(np.int32) if v.dtype == torch.int32 else a.view(np.int64)))
+    return res
+
+
+def test_dump_outputs_whole_arrays(tmp_path):
+    """--dump-outputs: every result array and both counters as float64 .npy, value for value (u32 is exact in f64)."""
+    import numpy as np
+
+    res = _results(1000, 37, 1)
+    bench.dump_outputs(str(tmp_path / "d"), res, FakeReceiver(res))
+    exp = res.to_numpy()
+    names = sorted(p.name for p in (tmp_path / "d").iterdir())
+    assert names == sorted([k + ".npy" for k in exp] + ["frame_index.npy"])
+    for k, v in exp.items():
+        got = np.load(tmp_path / "d" / (k + ".npy"))
+        assert got.dtype == np.float64 and got.shape == v.shape and np.array_equal(got, v.astype(np.float64))
+        assert np.array_equal(got.astype(v.dtype), v)
+    assert np.array_equal(np.load(tmp_path / "d" / "frame_index.npy"), np.arange(1000))
+
+
+def test_dump_outputs_samples_past_the_size_limit(tmp_path, monkeypatch):
+    """Past the byte limit the same seeded frames are taken from every per-frame array, run after run, and the files
+    stay within the limit; the counters are always whole."""
+    import numpy as np
+
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 16384)
+    res = _results(5001, 11, 2)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), res, FakeReceiver(res))
+    files = list((tmp_path / "a").iterdir())
+    assert sum(np.load(f).nbytes for f in files) <= 16384
+    idx = np.load(tmp_path / "a" / "frame_index.npy").astype(np.int64)
+    assert 0 < len(idx) < 5001 and np.all(np.diff(idx) > 0) and idx[-1] < 5001
+    exp = res.to_numpy()
+    for f in files:
+        a = np.load(f)
+        assert np.array_equal(a, np.load(tmp_path / "b" / f.name))
+        k = f.name[:-4]
+        if k in ("flow_counts", "verdict_counts"):
+            assert np.array_equal(a, exp[k].astype(np.float64))
+        elif k != "frame_index":
+            assert np.array_equal(a, exp[k][idx].astype(np.float64))

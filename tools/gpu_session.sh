@@ -21,6 +21,6 @@ python -c "import __graft_entry__ as g; assert g.lib_build_id() == g.tree_build_
 # s30: the round's final tree: GPU suite, smoke(), the default bench line, then the rocprofv3 evidence pass
 step gputest 900 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread
 step smoke 300 python -c "import __graft_entry__ as g; g.smoke(); print('{\"smoke\": \"ok\"}')"
-step bench 600 python bench.py
+step bench 600 python bench.py --full
 step profile 900 bash tools/profile_bench.sh r6j
 echo done

@@ -12,7 +12,7 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 cd /tmp
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -T -d $OUT/bench -o run --output-format csv -- \
-  python3 $R/bench.py --steps 50 --warmup 5 --cpu-seconds 2 --no-extras > $OUT/bench.json 2> $OUT/bench.err || exit 11
+  python3 $R/bench.py --steps 50 --warmup 5 --full --cpu-seconds 2 --no-extras > $OUT/bench.json 2> $OUT/bench.err || exit 11
 # traffic passes: one FETCH_SIZE and one WRITE_SIZE run per workload (name[:variant]: libos = the 36-byte LibOS record)
 for SPEC in c2_tcp1500 c3_udp64 c4_imix c5_tcp1500_10k c1_tcp1078 c3_udp64_random_ports c2_tcp1500:libos c2_tcp1500:txf; do
   WL=${SPEC%%:*}; VAR=${SPEC#*:}; [ "$VAR" = "$SPEC" ] && VAR=""
