@@ -192,10 +192,12 @@ DIAG_FUNCTIONS = [
     ("dk_diag_tcp_set_walk", c_int, [c_void_p, c_int32, c_int32]),
     ("dk_diag_tcp_last_walk", c_int, [c_void_p]),
     ("dk_diag_tcp_set_sort", c_int, [c_void_p, c_int32]),
+    ("dk_diag_tcp_last_sort", c_int, [c_void_p]),
 ]
 DK_DIAG_RX_KNOBS = ["stage", "split", "small", "sched", "grid", "grid_per_cu", "debug", "lds_table", "tail", "udp_table",
                     "host_zc"]
 DK_TCP_WALKS = {"lane": 0, "wave": 1, "relay": 2, "scan": 3}
+DK_TCP_SORTS = {"counting": 0, "radix": 1}
 
 ALL_FUNCTIONS = FUNCTIONS + RING_FUNCTIONS + TCP_FUNCTIONS + DIAG_FUNCTIONS + DEMI_FUNCTIONS + COMM_FUNCTIONS
 

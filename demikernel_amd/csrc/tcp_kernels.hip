@@ -1766,6 +1766,7 @@ struct dk_tcp_ctx {
     bool reordered = false;               // the last read count: >= 1 in kShapeStoredDen segments STORED
     int last_walk = -1;                   // the walk the last call ran (dk_diag_tcp_last_walk)
     int sort = -1;                        // dk_diag_tcp_set_sort: 1 the radix sort always, -1 the rule
+    int last_sort = -1;                   // the sort the last call ran (dk_diag_tcp_last_sort)
 };
 
 extern "C" {
@@ -1799,6 +1800,8 @@ int dk_tcp_ctx_create(int32_t device, dk_tcp_ctx** out) {
 }
 
 int dk_diag_tcp_last_walk(const dk_tcp_ctx* t) { return t ? t->last_walk : -1; }
+
+int dk_diag_tcp_last_sort(const dk_tcp_ctx* t) { return t ? t->last_sort : -1; }
 
 int dk_diag_tcp_set_walk(dk_tcp_ctx* t, int32_t walk, int32_t relay_waves) {
     if (!t || walk < -1 || walk > 3) return EINVAL;
@@ -1838,7 +1841,10 @@ int dk_tcp_rx_process(dk_tcp_ctx* t, const dk_rx_results* rx, uint32_t n, dk_tcp
     if (n > 0x7FFFFFFFu || nconns > 0x7FFFFFFFu ||
         (uint64_t)n + (uint64_t)DK_TCP_DELIV_EXTRA * nconns > 0xFFFFFFFFull)
         return EINVAL;
-    if (n == 0 && nconns == 0) return 0;
+    if (n == 0 && nconns == 0) {
+        t->last_sort = -1;
+        return 0;
+    }
     DeviceGuard g(t->device);
     const hipStream_t s = (hipStream_t)stream;
     int rc = 0;
@@ -1883,6 +1889,7 @@ int dk_tcp_rx_process(dk_tcp_ctx* t, const dk_rx_results* rx, uint32_t n, dk_tcp
     // kSortMaxRows table rows, else the radix sort and the range kernel
     const uint32_t nkeys = 2 * nconns + 1, ntiles = (n + dk_tcp::kSortTile - 1) / dk_tcp::kSortTile;
     const bool csort = nconns && n && nconns <= dk_tcp::kSortMaxRows && t->sort != 1;
+    t->last_sort = nconns && n ? (csort ? 0 : 1) : -1;
     if (csort) {
         const size_t hb = (size_t)nkeys * ntiles;
         if (t->used && t->csort_cap < hb && hipEventSynchronize(t->last) != hipSuccess) return EINVAL;

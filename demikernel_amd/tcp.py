@@ -90,6 +90,13 @@ class TcpReceiver:
         w = self.lib.dk_diag_tcp_last_walk(self._ctx)
         return {v: k for k, v in N.DK_TCP_WALKS.items()}.get(w)
 
+    @property
+    def last_sort(self) -> Optional[str]:
+        """The sort the last process() call ordered its batch with (dk_diag_tcp_last_sort: "counting" or "radix"),
+        None before the first and after a call with no segments or no table rows."""
+        s = self.lib.dk_diag_tcp_last_sort(self._ctx)
+        return {v: k for k, v in N.DK_TCP_SORTS.items()}.get(s)
+
     def close(self) -> None:
         if self._ctx:
             self.lib.dk_tcp_ctx_destroy(self._ctx)

@@ -70,6 +70,9 @@ int dk_diag_tcp_last_walk(const struct dk_tcp_ctx* ctx);
 /* How dk_tcp_rx_process orders the batch by connection: sort -1 the rule (one stable counting pass over the whole
  * key up to 255 table rows, rocPRIM's radix sort beyond), 1 the radix sort always. 0 or EINVAL. */
 int dk_diag_tcp_set_sort(struct dk_tcp_ctx* ctx, int32_t sort);
+/* The sort the context's last dk_tcp_rx_process call ordered its batch with (0 the counting pass, 1 the radix sort;
+ * -1 none yet, or a call with no segments or no table rows, which orders nothing by connection). */
+int dk_diag_tcp_last_sort(const struct dk_tcp_ctx* ctx);
 
 #ifdef __cplusplus
 }

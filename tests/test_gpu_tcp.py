@@ -347,5 +347,8 @@ def test_counting_sort_matches_radix(nconns, reorder):
         tcp = TcpReceiver(0, radix_sort=radix)
         got_t, got = gpu_process(tcp, table.copy(), r)
         torch.cuda.synchronize()
+        sort = tcp.last_sort  # dk_diag_tcp_last_sort: the rule's choice, and the forced one
         tcp.close()
+        assert sort == ("radix" if radix or len(table) > 255 else "counting"), (len(table), radix, sort)
         assert_same(got_t, got, exp_t, exp, f"{len(table)} rows reorder {reorder} radix {radix}")
+    assert len(table) == nconns + 1  # 254 flows: 255 rows, the counting pass's last; 255 flows: the radix sort's first
