@@ -39,15 +39,12 @@ constexpr uint32_t kPendUdp = 0xF1u;   // UDP header parsed; awaiting U3/demux
 constexpr uint32_t kPendIcmp = 0xF2u;  // ICMPv4 message >= 8 bytes; awaiting its checksum and type checks
 // ICMPv4 type bytes Icmpv4Type2::parse accepts (icmpv4/protocol.rs:37-56): 0, 3, 4, 5, 8 .. 14.
 constexpr uint32_t kIcmpTypes = (1u << 0) | (1u << 3) | (1u << 4) | (1u << 5) | (0x7Fu << 8);
-// Tuning knobs (compile-time; defaults are the measured best, see DESIGN.md "Tuning log").
+// Tuning knobs (compile-time; defaults are the measured best).
 #ifndef DK_COOP_U
 #define DK_COOP_U 6
 #endif
 #ifndef DK_HDR_TEMPORAL_U
 #define DK_HDR_TEMPORAL_U 1  // loads u < this of a frame's first iteration take the default policy (kHdrT)
-#endif
-#ifndef DK_HDR_TEMPORAL
-#define DK_HDR_TEMPORAL 0  // 1: the receive kernels too load each frame's first 256 bytes with the default policy
 #endif
 #ifndef DK_NT_LOADS
 #define DK_NT_LOADS 1
@@ -543,10 +540,7 @@ __device__ __forceinline__ void small_load(const FrameDesc<kShift>& F, const Blo
 #pragma unroll
     for (int k = 0; k < 4; k++) {
         const bool use = F.vec && !F.big && (uint32_t)(16 * k) < F.span;
-#ifndef DK_SMALL_LOAD_NT
-#define DK_SMALL_LOAD_NT 0
-#endif
-        const uint4 q = B.template ld<DK_SMALL_LOAD_NT != 0>(use ? off - F.sh + 16 * k : kOob);
+        const uint4 q = B.template ld<false>(use ? off - F.sh + 16 * k : kOob);
         R.w[4 * k + 0] = q.x;
         R.w[4 * k + 1] = q.y;
         R.w[4 * k + 2] = q.z;
@@ -640,7 +634,7 @@ __device__ __forceinline__ void coop_issue(uint32_t k0, uint32_t k1, uint32_t r,
             // policy instead of nontemporal, so the header-window rewrite finds its line in L2 (TX C2 -3 %; the
             // receive kernels measured +1.4 % with it)
             const uint32_t a = b < S.sl[h].nb ? S.sl[h].boff + 16 * b : kOob;
-            S.d[h][u] = ((kHdrT || DK_HDR_TEMPORAL) && u < DK_HDR_TEMPORAL_U && it == 0)
+            S.d[h][u] = (kHdrT && u < DK_HDR_TEMPORAL_U && it == 0)
                             ? B.template ld<false>(a)
                             : B.template ld<DK_NT_LOADS != 0>(a);
         }
@@ -798,14 +792,11 @@ __device__ __forceinline__ uint32_t seg_sum_fast(const Chunk& C, const WL& W, ui
     return MemAcc{f}.sum_le16(34, (uint32_t)E);
 }
 
-#ifndef DK_RES_STORE
-#define DK_RES_STORE 0  // result stores: 0 plain (nontemporal in the small-frame kernel), 1 nontemporal everywhere
-#endif
 // Result stores. The small-frame kernel stores nontemporal (C3 -3.7 %: its 20-24 B of results per 64-byte frame are
 // 28 % of its traffic); the other kernels measured ±0 either way (round 1) and keep plain stores.
 template <bool kNt = false>
 __device__ __forceinline__ void st_res(uint32_t* p, uint32_t v) {
-    if (kNt || DK_RES_STORE == 1)
+    if (kNt)
         __builtin_nontemporal_store(v, p);
     else
         *p = v;
@@ -1098,22 +1089,12 @@ __device__ __forceinline__ uint32_t opaque_v(uint32_t x) {
     asm volatile("" : "+v"(x));
     return x;
 }
-// An LDS add the compiler does not see as an LDS access: issued while the wave's LDS-DMA window is in flight (the
-// pipelined small-frame loop), a compiler-visible LDS atomic waits for the DMA first (it may alias the DMA's target);
-// these never do (the counters are not in any wave's window). No return value, so no wait of its own.
-__device__ __forceinline__ void lds_add_asm(uint32_t* p, uint32_t v) {
-    const uint32_t a = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t*)p;
-    asm volatile("ds_add_u32 %0, %1" ::"v"(a), "v"(v));
-}
-template <bool kAsm = false>
 __device__ __forceinline__ void flow_add(const RxParams& P, bool lds_flows, uint32_t* s_flow, uint32_t fid,
                                          uint32_t cnt) {
-    if (kAsm && lds_flows) lds_add_asm(&s_flow[fid >> 1], cnt << ((fid & 1u) * 16));
-    else if (lds_flows) atomicAdd(&s_flow[fid >> 1], cnt << ((fid & 1u) * 16));
+    if (lds_flows) atomicAdd(&s_flow[fid >> 1], cnt << ((fid & 1u) * 16));
     else if (P.flow_mode == kFlowGlobal)
         atomicAdd(reinterpret_cast<unsigned long long*>(P.res.flow_counts + fid), (unsigned long long)cnt);
 }
-template <bool kAsm = false>
 __device__ __forceinline__ void count_chunk(const RxParams& P, bool live, uint32_t lane, uint32_t v, uint32_t fid,
                                             bool lds_flows, uint32_t* s_flow, uint32_t* s_vh) {
     const bool dl = live && (v == DK_V_OK_TCP || v == DK_V_OK_UDP);
@@ -1122,19 +1103,18 @@ __device__ __forceinline__ void count_chunk(const RxParams& P, bool live, uint32
         const uint32_t leader = (uint32_t)__builtin_ctzll(todo);
         const uint32_t f0 = __builtin_amdgcn_readlane(fid, leader);
         const uint64_t m = __ballot(fid == f0) & todo;
-        if (lane == leader) flow_add<kAsm>(P, lds_flows, s_flow, opaque_v(f0), opaque_v((uint32_t)__popcll(m)));
+        if (lane == leader) flow_add(P, lds_flows, s_flow, opaque_v(f0), opaque_v((uint32_t)__popcll(m)));
         todo &= ~m;
         if (__popcll(m) < kFlowAggMin) break;
     }
-    if ((todo >> lane) & 1u) flow_add<kAsm>(P, lds_flows, s_flow, fid, 1u);
+    if ((todo >> lane) & 1u) flow_add(P, lds_flows, s_flow, fid, 1u);
     if (P.res.verdict_counts) {
         uint64_t todo = __ballot(live);
         while (todo) {
             const uint32_t leader = (uint32_t)__builtin_ctzll(todo);
             const uint32_t v0 = __builtin_amdgcn_readlane(v, leader);
             const uint64_t m = __ballot(live && v == v0);
-            if (kAsm && lane == leader) lds_add_asm(&s_vh[v0], (uint32_t)__popcll(m));
-            else if (lane == leader) atomicAdd(&s_vh[opaque_v(v0)], opaque_v((uint32_t)__popcll(m)));
+            if (lane == leader) atomicAdd(&s_vh[opaque_v(v0)], opaque_v((uint32_t)__popcll(m)));
             todo &= ~m;
         }
     }
@@ -1256,16 +1236,6 @@ struct TailQ {
 #ifndef DK_MIN_WAVES_ALIGNED
 #define DK_MIN_WAVES_ALIGNED DK_MIN_WAVES
 #endif
-#ifndef DK_STAGED_PRIO
-#define DK_STAGED_PRIO 0  // > 0: a wave streaming its chunk's frames issues at this priority, phase C at 0
-#endif
-#ifndef DK_STAGED_LATE_INIT
-#define DK_STAGED_LATE_INIT 0  // 1: the LDS init, table copy and barrier after a wave's first frame stream
-#endif
-#ifndef DK_TAIL_LATE
-#define DK_TAIL_LATE 0  // 1: a tail grab is for the next round (issued after this round's stream, resolved after its
-                        // phase C, the descriptors loaded then): committed half a round ahead instead of 1.5
-#endif
 template <bool kShift, bool kStage>
 __global__ __launch_bounds__(kBlock, kStage ? DK_MIN_WAVES_STAGED : kShift ? DK_MIN_WAVES : DK_MIN_WAVES_ALIGNED)
 void dk_rx_kernel(RxParams P) {
@@ -1283,18 +1253,12 @@ void dk_rx_kernel(RxParams P) {
     DK_STAMPW_RT(12);
     DK_STAMPW(0);
     const bool lds_flows = P.flow_mode == kFlowLds;
-    // the histograms' zeroing, the Active table's copy and the workgroup barrier: before the first chunk, or
-    // (DK_STAGED_LATE_INIT) after a wave's first frame stream, which needs none of them (a wave without a chunk at its
-    // end): the copy then overlaps the first stream
-    const auto init = [&]() {
-        for (uint32_t k = tid; k < DK_V_COUNT; k += kBlock) s_vh[k] = 0;
-        if (lds_flows)
-            for (uint32_t k = tid; k < P.flow_words; k += kBlock) s_flow[k] = 0;
-        lt_load(P, tid, kBlock);
-        __syncthreads();
-    };
-    constexpr bool kLateInit = DK_STAGED_LATE_INIT != 0 && kStage;
-    if (!kLateInit) init();
+    // the histograms' zeroing, the Active table's copy and the workgroup barrier, before the first chunk
+    for (uint32_t k = tid; k < DK_V_COUNT; k += kBlock) s_vh[k] = 0;
+    if (lds_flows)
+        for (uint32_t k = tid; k < P.flow_words; k += kBlock) s_flow[k] = 0;
+    lt_load(P, tid, kBlock);
+    __syncthreads();
     DK_STAMPW(1);
 
     const WaveRange r = wave_range(P.sched, P.n, wv, lane);
@@ -1304,7 +1268,6 @@ void dk_rx_kernel(RxParams P) {
     const uint32_t ks = dyn ? P.tail_ks : ~0u;  // chunks from round ks on come from the tail (host: ks >= 2)
     uint32_t c, lim, nc, nlim;
     bool have = r.chunk(0, c, lim);
-    const bool had = have;
     uint32_t noff = 0, nlen = 0;  // descriptors of this wave's next chunk
     if (have && c + r.lane_off < lim) {
         noff = P.off[c + r.lane_off];
@@ -1322,17 +1285,15 @@ void dk_rx_kernel(RxParams P) {
         const uint32_t i = c + lane;
         const bool live = i < lim;
         const uint32_t off = noff, len = nlen;
-        constexpr bool kLate = DK_TAIL_LATE != 0;
-        const bool late = kLate && k + 1 >= ks;  // wave-uniform: the next chunk comes from a grab issued this round
         if (k + 1 < ks) {
             have = r.chunk(k + 1, nc, nlim);
-        } else if (!kLate) {  // the tail: the chunk grabbed a round ago
+        } else {  // the tail: the chunk grabbed a round ago
             const uint32_t j = Q.resolve(P);
             have = j != kNoChunk;
             nc = 64 * j;
             nlim = P.n;
         }
-        if (!late && have && nc + lane < nlim) {  // prefetch the next chunk's descriptors
+        if (have && nc + lane < nlim) {  // prefetch the next chunk's descriptors
             noff = P.off[nc + lane];
             nlen = P.len[nc + lane];
         }
@@ -1342,35 +1303,21 @@ void dk_rx_kernel(RxParams P) {
         Chunk C;
         if (k < 3) DK_STAMPW(2 + 3 * k);
         DK_MARK(stream);
-        if (DK_STAGED_PRIO) __builtin_amdgcn_s_setprio(DK_STAGED_PRIO);  // the frame stream issues ahead of phase C
         stream_chunk<kShift, false, kStage ? kRoundsStaged : kRoundsPerStep>(P.frames, P.frames_bytes, live, lane, W, off,
                                                                               len, C);
         // the grab for chunk k + 2, resolved at the top of the next round: issued after the frame stream (its return
         // register would be live through the stream's load registers, the kernel's register peak); phase C covers
         // its latency
-        if (kLate ? late : have && k + 2 >= ks) Q.issue(P, lane);
-        if (kLateInit && k == 0) init();
+        if (have && k + 2 >= ks) Q.issue(P, lane);
         if (k < 3) DK_STAMPW(3 + 3 * k);
         DK_ACC_SPLIT(0);
-        if (DK_STAGED_PRIO) __builtin_amdgcn_s_setprio(0);
         DK_MARK(phaseC);
         rx_finish<kShift, kStage>(P, i, live, lane, W, off, len, C, v, fid, rec);
         if (k < 3) DK_STAMPW(4 + 3 * k);
         DK_ACC_SPLIT(1);
         // The next chunk's descriptors (loaded a chunk ago) are waited for here, before this chunk's stores: used first
         // at the top of the next chunk, after a staged flush, their wait also waited for every store's write ack.
-        if (late) {  // DK_TAIL_LATE: resolve this round's grab; staging and counting cover the descriptors' latency
-            const uint32_t j = Q.resolve(P);
-            have = j != kNoChunk;
-            nc = 64 * j;
-            nlim = P.n;
-            if (have && nc + lane < nlim) {
-                noff = P.off[nc + lane];
-                nlen = P.len[nc + lane];
-            }
-        } else {
-            asm volatile("" ::"v"(noff), "v"(nlen));
-        }
+        asm volatile("" ::"v"(noff), "v"(nlen));
         DK_MARK(stage);
         if (kStage) {  // the last kStageK chunks' results; stored when full and at exit
             stage_put(stg, rec);
@@ -1388,7 +1335,6 @@ void dk_rx_kernel(RxParams P) {
         DK_MARK(loop_tail);
     }
 
-    if (kLateInit && !had) init();  // a wave without a chunk: its share of the copy and the barrier
     DK_STAMPW(11);
     DK_MARK(epilogue);
     DK_ACC_BEGIN();
@@ -1426,23 +1372,11 @@ constexpr uint32_t kWinLoads = (kWinGran + 63) / 64;  // DMA loads for a full wi
 // kUb: the last granules share the window's LDS (the general pass runs after the main loop's last window), leaving
 // room for the LDS bind table at three workgroups per CU; measured 3 % slower at C3 with the port table, so the
 // instantiation without the table keeps them apart (session r05zo).
-#ifndef DK_SMALL_LDS_UNION
-#define DK_SMALL_LDS_UNION 0  // 1: the general pass's last granules share the window's LDS in every instantiation
-#endif
 template <bool kUb>
 struct SmallLds {
     uint4 tail[64];             // the general pass: the last granule of each big frame (seg_sum_fast)
     uint4 win[kWinLoads * 64];  // the main loop: the chunk's frame window (whole 1 KiB DMA pieces)
 };
-#if DK_SMALL_LDS_UNION
-template <>
-struct SmallLds<false> {
-    union {
-        uint4 win[kWinLoads * 64];
-        uint4 tail[64];
-    };
-};
-#endif
 template <>
 struct SmallLds<true> {
     union {
@@ -1603,18 +1537,6 @@ __device__ __forceinline__ void small_big_frames(const FrameDesc<kShift>& F, uin
 #ifndef DK_SMALL_PRIO
 #define DK_SMALL_PRIO 1
 #endif
-#ifndef DK_SMALL_LATE_BARRIER
-#define DK_SMALL_LATE_BARRIER 0
-#endif
-#ifndef DK_SMALL_PIPE
-#define DK_SMALL_PIPE 0  // 1: the next window's DMA in flight through a chunk's stores and counts (round 6: +5 % on C3)
-#endif
-// A workgroup barrier that orders LDS only (no wait for the wave's outstanding global loads and stores).
-__device__ __forceinline__ void lds_barrier() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
 template <bool kShift>
 __device__ __forceinline__ bool small_fast_eligible(const FrameDesc<kShift>& F, uint32_t len, const RegAcc& R) {
     const bool ihl5 = ((R.w[3] >> 16) & 0x0Fu) == 5u;
@@ -1622,15 +1544,9 @@ __device__ __forceinline__ bool small_fast_eligible(const FrameDesc<kShift>& F, 
     const bool topt = R.b8(23) == 6u && (R.b8(46) >> 4) > 5u;
     return F.vec && !F.big && len >= 34 && ihl5 && !arp && !topt;
 }
-struct NoMid {
-    __device__ __forceinline__ void operator()() const {}
-};
-// mid(): called between the verdicts (every socket-table load waited for) and the result stores: the pipelined loop
-// issues the next window's DMA there. (Issued right after the table load, the compiler waited for the DMA with it:
-// it counts LDS-DMA and loads as events that may complete out of order, so only vmcnt(0) covers the table load.)
-template <bool kOpt, bool kUb, class Mid = NoMid>
+template <bool kOpt, bool kUb>
 __device__ __forceinline__ void small_fast(const RxParams& P, uint32_t i, bool live, uint32_t lane, const RegAcc& R,
-                                           uint32_t len, uint32_t& v_out, uint32_t& fid_out, const Mid& mid = Mid()) {
+                                           uint32_t len, uint32_t& v_out, uint32_t& fid_out) {
     Lane L;
     parse_fast(R, len, P, L);
     if (!live) {
@@ -1690,7 +1606,6 @@ __device__ __forceinline__ void small_fast(const RxParams& P, uint32_t i, bool l
         }
     }
     const uint32_t v = L.v;
-    mid();
     if (live) {
         const bool full = v <= DK_V_ICMP || v == DK_V_TCP_NOSOCK || v == DK_V_UDP_NOSOCK;
         const bool is_tcp = v == DK_V_OK_TCP || v == DK_V_TCP_NOSOCK;
@@ -1748,11 +1663,7 @@ __global__ __launch_bounds__(SmallShape<kUb>::kBlock, DK_MIN_WAVES_SMALL) void d
     if (lds_flows)
         for (uint32_t k = tid; k < P.flow_words; k += kSmallBlock) s_flow[k] = 0;
     if (kUb) ub_load(P, tid, kSmallBlock);
-    // Without the LDS bind table the counters are the only shared LDS state: the barrier that orders their zeroing
-    // before any count can wait until the first chunk's counts (kLateBarrier), off the first window's path.
-    constexpr bool kLateBarrier = DK_SMALL_LATE_BARRIER && !kUb;
-    const bool have0 = have;
-    if (!kLateBarrier) __syncthreads();
+    __syncthreads();
     DK_STAMP(11);
     // The grid is one generation of waves and the chunks do not divide evenly: the waves with one chunk more than the
     // rest (the last round's) set the launch's length, so they issue first on their SIMD (s_setprio; round 4: C3
@@ -1775,33 +1686,6 @@ __global__ __launch_bounds__(SmallShape<kUb>::kBlock, DK_MIN_WAVES_SMALL) void d
     // wave-uniform: bit k set = chunk k (< 64) stored its deferral mask; chunks from 64 on always store theirs
     uint64_t had = 0;
     DK_ACC_DECL;
-    // kPipe (no LDS bind table; its general-pass granules share the window's LDS): chunk k + 1's window DMA is issued
-    // inside chunk k, once k's verdicts are decided (its socket-table loads waited for), and is in flight through k's
-    // result stores, counts and the loop's turn; chunk k + 3's descriptors come by LDS-DMA into
-    // the wave's general-pass granule slots with it (registers holding a load in flight would be waited for at the
-    // loop's turn) and are read out at the top of chunk k + 1. The counts' LDS adds are inline asm: a compiler-visible
-    // LDS atomic would first wait for the pending DMA.
-    constexpr bool kPipe = DK_SMALL_PIPE != 0 && !kUb;
-    WinPlan pl{false, 0};
-    uint32_t* const dsc = reinterpret_cast<uint32_t*>(&W.tail[0]);  // [0, 64): offsets; [64, 97): length dwords
-    // Chunk j's descriptors into dsc: 64 offsets, and the 33 dwords covering its 64 lengths from the 4-byte boundary
-    // below &len[j] (the length array is only 2-byte aligned); every load stays inside a dword that holds an element.
-    const auto desc_dma = [&](uint32_t cj, uint32_t limj, uint32_t ln) {
-        const uint32_t o = min(cj + ln, limj - 1);
-        __builtin_amdgcn_global_load_lds(P.off + o, (lds_void*)dsc, 4, 0, 0);
-        if (ln < 33) {
-            const uintptr_t lb = reinterpret_cast<uintptr_t>(P.len + cj) & ~(uintptr_t)3;
-            const uintptr_t hi = (reinterpret_cast<uintptr_t>(P.len + limj) - 1) & ~(uintptr_t)3;
-            const uintptr_t la = min(lb + 4 * (uintptr_t)ln, hi);
-            __builtin_amdgcn_global_load_lds(reinterpret_cast<const void*>(la), (lds_void*)(dsc + 64), 4, 0, 0);
-        }
-    };
-    if (kPipe && have) {
-        const uint32_t ln = lane_id();
-        pl = small_window_issue(F, B, off, len, c + ln < lim, ln, W);
-        uint32_t c2p, lim2p;
-        if (have1 && r.chunk(2, c2p, lim2p)) desc_dma(c2p, lim2p, ln);
-    }
     for (uint32_t k = 0; have; k++) {
         DK_ACC_BEGIN();
         // the lane id re-materialised per chunk (as in dk_rx_kernel): lane-derived constants are not held in VGPRs
@@ -1813,7 +1697,7 @@ __global__ __launch_bounds__(SmallShape<kUb>::kBlock, DK_MIN_WAVES_SMALL) void d
         const bool live = i < lim;
         const bool have2 = have1 && r.chunk(k + 2, c2, lim2);
         uint32_t off2 = 0, len2 = 0;
-        if (!kPipe && have2 && c2 + lane < lim2) {  // descriptors two chunks ahead, before this chunk's window DMA
+        if (have2 && c2 + lane < lim2) {  // descriptors two chunks ahead, before this chunk's window DMA
             off2 = P.off[c2 + lane];
             len2 = P.len[c2 + lane];
         }
@@ -1821,17 +1705,8 @@ __global__ __launch_bounds__(SmallShape<kUb>::kBlock, DK_MIN_WAVES_SMALL) void d
         uint32_t v, fid;
         if (k == 0) DK_STAMP(1);
         DK_MARK(s_window);
-        if (!kPipe) pl = small_window_issue(F, B, off, len, live, lane, W);
+        const WinPlan pl = small_window_issue(F, B, off, len, live, lane, W);
         small_window_read(pl, F, B, off, W, C.R);  // waits for every load and store in flight (vmcnt 0)
-        if (kPipe && have2) {  // chunk k + 2's descriptors, DMA'd during chunk k - 1 (or before the loop)
-            const uint32_t sh = (uint32_t)(reinterpret_cast<uintptr_t>(P.len + c2) & 3u) + 2 * lane;
-            const uint32_t o2 = dsc[lane], l2 = (dsc[64 + (sh >> 2)] >> ((sh & 3u) * 8)) & 0xFFFFu;
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // read out before chunk k + 3's DMA reuses the slots
-            if (c2 + lane < lim2) {
-                off2 = o2;
-                len2 = l2;
-            }
-        }
         if (k < 3) DK_STAMP(2 + 3 * k);
         DK_MARK(s_eligible);
         DK_ACC_SPLIT(0);
@@ -1843,22 +1718,11 @@ __global__ __launch_bounds__(SmallShape<kUb>::kBlock, DK_MIN_WAVES_SMALL) void d
         const uint64_t dm = __ballot(live && !take);
         deferred = deferred || dm != 0;
         DK_MARK(s_fast);
-        if (kPipe) {
-            const auto mid = [&]() {
-                uint32_t c3, lim3;
-                if (have2 && r.chunk(k + 3, c3, lim3)) desc_dma(c3, lim3, lane);
-                if (have1) pl = small_window_issue(F1, B, off1, len1, c1 + lane < lim1, lane, W);
-                asm volatile("" ::: "memory");  // issued here, not sunk to the loop's end (the compiler did)
-            };
-            small_fast<kOpt, kUb>(P, i, take, lane, C.R, len, v, fid, mid);
-        } else {
-            small_fast<kOpt, kUb>(P, i, take, lane, C.R, len, v, fid);
-        }
+        small_fast<kOpt, kUb>(P, i, take, lane, C.R, len, v, fid);
         if (k < 3) DK_STAMP(3 + 3 * k);
         DK_ACC_SPLIT(1);
-        if (kLateBarrier && k == 0) lds_barrier();  // every wave of the workgroup arrives once (below if no chunk)
         DK_MARK(s_count);
-        count_chunk<kPipe>(P, take, lane, v, fid, lds_flows, s_flow, s_vh);
+        count_chunk(P, take, lane, v, fid, lds_flows, s_flow, s_vh);
         DK_MARK(s_loop_tail);
         if (dm != 0 || k >= 64) {  // read back by this wave after the loop
             if (lane == 0) P.defer[k * nw + gw] = dm;
@@ -1881,7 +1745,6 @@ __global__ __launch_bounds__(SmallShape<kUb>::kBlock, DK_MIN_WAVES_SMALL) void d
         len1 = len2;
     }
     DK_MARK(s_epilogue);
-    if (kLateBarrier && !have0) lds_barrier();
     DK_ACC_BEGIN();
     if (deferred) {  // the general pass over the frames the loop left (byte path, streamed frames, options, ARP)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's mask stores
@@ -2251,9 +2114,6 @@ __device__ __noinline__ uint32_t tx_slow(uint8_t* f, uint32_t len) {
     return tx_pair(ipc, true, c);
 }
 
-#ifndef DK_TX_LINE128
-#define DK_TX_LINE128 0  // 1: frames of >= 128 bytes on a 128-byte boundary rewrite their whole first 128-byte line
-#endif
 // A frame's rewritten 64-byte header window, held in registers by the split TX kernel's finish waves until a burst.
 constexpr uint32_t kNoWin = 0xFFFFFFFFu;
 struct TxWin {
@@ -2318,18 +2178,6 @@ __device__ __forceinline__ void tx_finish(const TxParams& P, uint32_t lane, cons
         }
         typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
         const auto q = gptr(reinterpret_cast<u32x4*>(f));
-        if (DK_TX_LINE128 && len >= 128 && (reinterpret_cast<uintptr_t>(f) & 127u) == 0) {
-            // the frame's whole first 128-byte line (the L2 line): bytes [64, 128) read back (an L2 hit: kHdrT loads
-            // them temporally) so the line goes out whole
-            u32x4 e[4];
-#pragma unroll
-            for (int k = 0; k < 4; k++) e[k] = q[4 + k];
-#pragma unroll
-            for (int k = 0; k < 4; k++) q[k] = u32x4{d[4 * k], d[4 * k + 1], d[4 * k + 2], d[4 * k + 3]};
-#pragma unroll
-            for (int k = 0; k < 4; k++) q[4 + k] = e[k];
-            return;
-        }
 #pragma unroll
         for (int k = 0; k < 4; k++) q[k] = u32x4{d[4 * k], d[4 * k + 1], d[4 * k + 2], d[4 * k + 3]};
         return;
