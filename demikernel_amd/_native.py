@@ -75,6 +75,24 @@ class DkRxResults(ctypes.Structure):
     _fields_ = [(name, c_void_p) for name in RESULT_FIELDS]
 
 
+# dk_tx_serialize (include/dk_rx.h): enum dk_tx_status, the offload flags, struct dk_tx_link and struct dk_tx_segs.
+TX_STATUSES = ["OK", "E_PROTO", "E_OPTS", "E_LINK", "E_LEN", "E_RANGE"]
+DK_TX_OK, DK_TX_E_PROTO, DK_TX_E_OPTS, DK_TX_E_LINK, DK_TX_E_LEN, DK_TX_E_RANGE = range(6)
+DK_TX_OFFLOAD_TCP, DK_TX_OFFLOAD_UDP = 1, 2
+TX_LINK_DTYPE = np.dtype([("dst_mac", "u1", (6,)), ("src_mac", "u1", (6,)), ("reserved", "<u4")])
+assert TX_LINK_DTYPE.itemsize == 16
+TX_SEG_FIELDS = ["payload_off", "payload_len", "meta", "src_ip", "dst_ip", "ports", "tcp_seq", "tcp_ack", "tcp_win",
+                 "tcp_opts", "ip_word", "link"]
+
+
+class DkTxLink(ctypes.Structure):
+    _fields_ = [("dst_mac", c_uint8 * 6), ("src_mac", c_uint8 * 6), ("reserved", c_uint32)]
+
+
+class DkTxSegs(ctypes.Structure):
+    _fields_ = [(name, c_void_p) for name in TX_SEG_FIELDS] + [("n", c_uint32), ("flags", c_uint32)]
+
+
 # (name, restype, argtypes) of every function include/dk_rx.h declares.
 FUNCTIONS = [
     ("dk_rx_ctx_create", c_int, [POINTER(DkRxCfg), POINTER(c_void_p)]),
@@ -90,6 +108,9 @@ FUNCTIONS = [
                                                c_void_p]),
     ("dk_tx_checksum", c_int, [c_void_p, c_uint64, c_void_p, c_void_p, c_uint32, c_void_p]),
     ("dk_tx_checksum_fields", c_int, [c_void_p, c_uint64, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p]),
+    ("dk_tx_header_bytes", c_uint32, [c_uint32, c_void_p]),
+    ("dk_tx_serialize", c_int, [c_void_p, c_uint64, POINTER(DkTxSegs), c_void_p, c_uint32, c_void_p, c_void_p, c_void_p,
+                                c_void_p]),
     ("dk_rx_verdict_name", c_char_p, [c_int]),
     ("dk_rx_verdict_errno", c_int, [c_int]),
     ("dk_rx_abi_version", c_uint32, []),
@@ -189,6 +210,7 @@ DIAG_FUNCTIONS = [
     ("dk_diag_path_stats_read", c_int, [c_void_p, c_void_p]),
     ("dk_diag_rx_set_tuning", c_int, [c_void_p, c_void_p, c_uint32]),
     ("dk_diag_tx_set_tuning", c_int, [c_int32, c_int32, c_int32]),
+    ("dk_diag_tx_serialize_set_grid", c_int, [c_int32]),
     ("dk_diag_tcp_set_walk", c_int, [c_void_p, c_int32, c_int32]),
     ("dk_diag_tcp_last_walk", c_int, [c_void_p]),
     ("dk_diag_tcp_set_sort", c_int, [c_void_p, c_int32]),

@@ -193,6 +193,47 @@ struct TxParams {
                        // are only read)
 };
 
+// TX serialize (dk_tx_serialize): headers built in the headroom in front of each payload.
+struct TxSerParams {
+    uint8_t* frames;
+    uint64_t frames_bytes;
+    dk_tx_segs segs;
+    const dk_tx_link* links;
+    uint32_t nlinks;
+    uint32_t sched;  // as RxParams::sched
+    uint32_t* off_out;
+    uint16_t* len_out;
+    uint32_t* status;  // nullable
+};
+
+// TcpHeader::compute_size (tcp/header.rs:408-421) of an option list: 20 + the entries' sizes (TcpOptions2::compute_size
+// :43-54; a SACK entry's blocks must lie inside sack[]) + one EndOfOptionsList byte when the list is not empty, rounded
+// up to 4. 0 when the list cannot be serialized (more than 5 entries, unknown kind, SACK with 0 or > 4 blocks, more
+// than the 60 bytes a data offset can express). Shared by dk_tx_header_bytes (host) and the kernel.
+DK_HD uint32_t tx_tcp_header_bytes(const dk_tcp_opts* o) {
+    if (!o || o->num == 0) return 20;
+    if (o->num > 5) return 0;
+    uint32_t size = 20;
+    for (uint32_t k = 0; k < o->num; k++) {
+        const uint32_t kind = o->opt[k].kind;
+        if (kind == 0) continue;
+        if (kind == 1) size += 1;
+        else if (kind == DK_TCPOPT_MSS) size += 4;
+        else if (kind == DK_TCPOPT_WS) size += 3;
+        else if (kind == DK_TCPOPT_SACK_OK) size += 2;
+        else if (kind == DK_TCPOPT_TS) size += 10;
+        else if (kind == DK_TCPOPT_SACK) {
+            const uint32_t ns = o->opt[k].u8, first = o->opt[k].u16;
+            if (ns < 1 || ns > 4 || first + ns > 4) return 0;
+            size += 2 + 8 * ns;
+        } else {
+            return 0;
+        }
+    }
+    size = (size + 1 + 3) & ~3u;
+    return size <= 60 ? size : 0;
+}
+
 }  // namespace dk
 
 // Launchers implemented in rx_kernels.hip (internal symbols, not part of the C ABI).
@@ -210,3 +251,5 @@ uint32_t dk_rx_small_block_waves(bool ub);  // waves per workgroup of the small-
 int dk_rx_process_ring_host(struct dk_rx_ctx* c, const dk_rx_batch* b, const dk_rx_results* r);
 int dk_tx_resident_blocks();  // occupancy of dk_tx_kernel per CU (0 on error)
 int dk_launch_tx(const dk::TxParams& p, uint32_t grid, void* stream);
+int dk_tx_serialize_resident_blocks();  // occupancy of dk_tx_serialize_kernel per CU (0 on error)
+int dk_launch_tx_serialize(const dk::TxSerParams& p, uint32_t grid, void* stream);

@@ -470,6 +470,7 @@ int ensure_stage(Stage& s, uint32_t cap, uint64_t bytes, bool opts) {
 // TX tuning overrides (-1 = host rule), set only by dk_diag_tx_set_tuning (never from the environment).
 struct TxTuning {
     std::atomic<int32_t> split{-1}, sched{-1}, grid_per_cu{-1};
+    std::atomic<int32_t> serialize_grid{-1};  // dk_diag_tx_serialize_set_grid
 };
 TxTuning& tx_tuning() {
     static TxTuning t;
@@ -912,6 +913,11 @@ int dk_diag_tx_set_tuning(int32_t split, int32_t sched, int32_t grid_per_cu) {
     return 0;
 }
 
+int dk_diag_tx_serialize_set_grid(int32_t grid) {
+    tx_tuning().serialize_grid = grid;
+    return 0;
+}
+
 namespace {
 // dk_tx_checksum / dk_tx_checksum_fields: persistent grid on the current device, the receive kernel's schedule rule.
 int tx_launch(uint8_t* frames, uint64_t frames_bytes, const uint32_t* off, const uint16_t* len, uint32_t n,
@@ -954,6 +960,44 @@ int dk_tx_checksum_fields(const uint8_t* frames, uint64_t frames_bytes, const ui
     if (n && !fields) return EINVAL;
     // the kernels only read the frames in this form (TxParams::fields set)
     return tx_launch(const_cast<uint8_t*>(frames), frames_bytes, off, len, n, fields, stream);
+}
+
+uint32_t dk_tx_header_bytes(uint32_t ip_protocol, const dk_tcp_opts* opts) {
+    if (ip_protocol == 17u) return 42;
+    if (ip_protocol != 6u) return 0;
+    const uint32_t hl = dk::tx_tcp_header_bytes(opts);
+    return hl ? 34 + hl : 0;
+}
+
+// dk_tx_serialize: persistent grid on the current device (dk_tx_kernel's shape: round-robin 256-segment tiles).
+int dk_tx_serialize(uint8_t* frames, uint64_t frames_bytes, const dk_tx_segs* segs, const dk_tx_link* links,
+                    uint32_t nlinks, uint32_t* off_out, uint16_t* len_out, uint32_t* status, void* stream) {
+    if (!segs) return EINVAL;
+    if (frames_bytes > DK_RX_MAX_BLOB) return EINVAL;
+    if (segs->n == 0) return 0;
+    if (!frames || !segs->payload_off || !segs->payload_len || !segs->meta || !segs->src_ip || !segs->dst_ip ||
+        !segs->ports || !links || nlinks == 0 || !off_out || !len_out)
+        return EINVAL;
+    static thread_local int dev_cached = -1;
+    static thread_local uint32_t cus = 0, occ = 0;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return EIO;
+    if (dev != dev_cached) {
+        int c = 0;
+        if (hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || c <= 0)
+            return EIO;
+        cus = (uint32_t)c;
+        occ = (uint32_t)std::max(dk_tx_serialize_resident_blocks(), 1);
+        dev_cached = dev;
+    }
+    dk::TxSerParams p{frames, frames_bytes, *segs, links, nlinks, 0u, off_out, len_out, status};
+    const TxTuning& T = tx_tuning();
+    if (T.sched >= 0) p.sched = (uint32_t)std::min<int32_t>(T.sched, 1);
+    uint32_t per_cu = std::min<uint32_t>(occ, 4u);
+    if (T.grid_per_cu > 0) per_cu = (uint32_t)T.grid_per_cu;
+    uint32_t grid = std::min((segs->n + 255) / 256, per_cu * cus);
+    if (T.serialize_grid > 0) grid = std::min(grid, (uint32_t)T.serialize_grid);
+    return dk_launch_tx_serialize(p, grid, stream);
 }
 
 const char* dk_rx_verdict_name(int v) {

@@ -2279,6 +2279,279 @@ __global__ __launch_bounds__(kBlock, DK_MIN_WAVES) void dk_tx_kernel(TxParams P)
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// TX serialize (dk_tx_serialize, dk_rx.h): the inverse of the receive kernel. For every segment the Ethernet2, IPv4 and
+// TCP / UDP headers are built in the headroom in front of the payload, as
+//   TcpHeader::serialize_and_attach (tcp/header.rs:330-405) / UdpHeader::serialize_and_attach (udp/header.rs:97-130),
+//   Ipv4Header::serialize_and_attach (ipv4/header.rs:229-266), Ethernet2Header::serialize_and_attach
+//   (ethernet2/header.rs:68-73)
+// build them. dk_tx_kernel's persistent schedule, one segment per lane, 64-segment chunks. What is streamed
+// (stream_chunk) is the PAYLOAD, as if (payload_off, payload_len) were a frame: every L4 header is an even number of
+// bytes, so the payload's 16-bit word grid is the segment's, and the payload's LE-half sum is the only part of the
+// checksum that comes from memory. The header's contribution is arithmetic on the descriptor fields in registers: no
+// header byte is ever read (the headroom holds garbage before the call, by contract).
+//
+// Concurrent neighbours: the granules holding a payload's first and last bytes may also hold header room (this
+// segment's own before the payload, another segment's after it) that another wave may be writing at the same moment.
+// Every such byte is masked out of the register window that the load filled (spans <= 64), or subtracted using the
+// value of that same load (streamed spans: granule 0 through W.hdr in coop_gather, the last granule through W.tail
+// below), never read a second time. A segment's own header is stored after its payload loads have returned (the stores
+// depend on the checksum).
+// ---------------------------------------------------------------------------------------------------------------------
+// The option bytes of one TCP header (TcpOptions2::serialize :56-101 per entry, then the EndOfOptionsList byte and the
+// zero padding, :382-395) written at p[0 .. nbytes); returns their LE-half sum (nbytes is even, p's parity is free).
+// Option-bearing segments are the rare ones (SYN, SACK): byte stores, one lane per segment. The list was validated by
+// tx_tcp_header_bytes.
+struct OptOut {
+    uint8_t* p;
+    uint32_t pos, sum;
+    __device__ __forceinline__ void put(uint32_t b) {
+        b &= 0xFFu;
+        p[pos] = (uint8_t)b;
+        sum += (pos & 1u) ? b << 8 : b;
+        pos++;
+    }
+    __device__ __forceinline__ void put16(uint32_t v) { put(v >> 8); put(v); }
+    __device__ __forceinline__ void put32(uint32_t v) { put16(v >> 16); put16(v); }
+};
+__device__ __noinline__ uint32_t tx_emit_options(const dk_tcp_opts* o, uint8_t* p, uint32_t nbytes) {
+    OptOut w{p, 0, 0};
+    const uint32_t num = o->num;
+    for (uint32_t k = 0; k < num; k++) {
+        const uint32_t kind = o->opt[k].kind;
+        if (kind == 0) continue;
+        w.put(kind);
+        if (kind == DK_TCPOPT_MSS) {
+            w.put(4);
+            w.put16(o->opt[k].u16);
+        } else if (kind == DK_TCPOPT_WS) {
+            w.put(3);
+            w.put(o->opt[k].u8);
+        } else if (kind == DK_TCPOPT_SACK_OK) {
+            w.put(2);
+        } else if (kind == DK_TCPOPT_SACK) {
+            const uint32_t ns = o->opt[k].u8, first = o->opt[k].u16;
+            w.put(2 + 8 * ns);
+            for (uint32_t s = 0; s < ns; s++) {
+                w.put32(o->sack[first + s][0]);
+                w.put32(o->sack[first + s][1]);
+            }
+        } else if (kind == DK_TCPOPT_TS) {
+            w.put(10);
+            w.put32(o->opt[k].v0);
+            w.put32(o->opt[k].v1);
+        }
+    }
+    while (w.pos < nbytes) w.put(0);  // EndOfOptionsList, then the padding
+    return w.sum;
+}
+
+// LE-half sum of payload bytes [0, len) from what stream_chunk left (payload = the streamed "frame").
+__device__ __forceinline__ uint32_t tx_payload_sum(const Chunk& C, const WaveLds& W, uint32_t lane, const uint8_t* pay,
+                                                   uint32_t len) {
+    if (!C.vec) return MemAcc{pay}.sum_le16(0, len);  // odd address: byte path
+    if (C.big) {
+        // fsum runs to the end of the last granule; the bytes past the payload end come off using the granule as it
+        // was loaded (they may be a neighbour's header room)
+        const int t0 = (int)(16 * C.nblk - C.sh) - 16;  // payload offset of the last granule's first byte
+        const uint4 a = W.tail[lane];
+        return C.fsum - block_sum_masked(a.x, a.y, a.z, a.w, (int)len - t0, 16, 0);
+    }
+    // the register window holds payload bytes [0, 64): dword k keeps its bytes below len
+    const int t = 32 - 8 * (int)len;
+    uint32_t acc = 0;
+#pragma unroll
+    for (int k = 0; k < 16; k++) {
+        const uint32_t sh = (uint32_t)min(max(t + 32 * k, 0), 32);
+        acc = hsum2(C.R.w[k] & (uint32_t)(0xFFFFFFFFull >> sh), acc);
+    }
+    return acc;
+}
+
+__device__ __forceinline__ uint32_t be16_sum(uint32_t x) { return (x >> 16) + (x & 0xFFFFu); }  // the BE words of a u32
+// BE words of an address held in octet order (dk_rx.h conventions).
+__device__ __forceinline__ uint32_t ip_be_sum(uint32_t a) { return bswap16(a & 0xFFFFu) + bswap16(a >> 16); }
+
+// The first hb bytes (42 or 54: Ethernet2 + IPv4 + UDP, or + the fixed TCP header) of a header, given as LE dwords
+// d[0 .. 13], stored at a. Even a: a 16-bit head when a is 2 mod 4, then dwords up to the next 16-byte boundary, 16-byte
+// stores while four dwords are left, dwords again, and a 16-bit tail when a is 0 mod 4. The common layouts are wide:
+// a 16-byte aligned payload behind a 54-byte header puts a at 10 mod 16 (16-bit, dword, three 16-byte stores), a
+// 64-byte aligned frame slot puts it at 0 (three 16-byte stores, dword, 16-bit). Odd a: byte stores. Every index into d
+// is a compile-time constant (registers, no scratch): one unrolled store sequence per count of leading dwords.
+template <int kLead>
+__device__ __forceinline__ void tx_store_dwords(uint8_t* base, const uint32_t (&e)[13], uint32_t ndw) {
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    const auto q = gptr(reinterpret_cast<uint32_t*>(base));
+#pragma unroll
+    for (int k = 0; k < kLead; k++)
+        if ((uint32_t)k < ndw) q[k] = e[k];
+#pragma unroll
+    for (int k = kLead; k < 13; k += 4) {
+        if (k + 4 <= 13 && (uint32_t)(k + 4) <= ndw) {
+            *gptr(reinterpret_cast<u32x4*>(base + 4 * k)) = u32x4{e[k], e[k + 1 < 13 ? k + 1 : 12],
+                                                                    e[k + 2 < 13 ? k + 2 : 12], e[k + 3 < 13 ? k + 3 : 12]};
+        } else {
+#pragma unroll
+            for (int m = k; m < k + 4 && m < 13; m++)
+                if ((uint32_t)m < ndw) q[m] = e[m];
+        }
+    }
+}
+__device__ __forceinline__ void tx_store_header(uint8_t* a, const uint32_t (&d)[14], bool tcp) {
+    const uint32_t am = (uint32_t)reinterpret_cast<uintptr_t>(a);
+    const uint32_t ndw = tcp ? 13u : 10u;  // whole dwords between head and tail: (hb - 2) / 4
+    if (am & 1u) {
+        const auto g = gptr(a);
+#pragma unroll
+        for (int k = 0; k < 54; k++)
+            if (tcp || k < 42) g[k] = (uint8_t)(d[k >> 2] >> ((k & 3) * 8));
+        return;
+    }
+    uint32_t e[13];
+    const uint32_t b = am & 2u;  // funnel-shift byte count: 0 or 2
+#pragma unroll
+    for (int k = 0; k < 13; k++) e[k] = __builtin_amdgcn_alignbyte(d[k + 1], d[k], b);
+    if (b) *gptr(reinterpret_cast<uint16_t*>(a)) = (uint16_t)d[0];
+    const uint32_t lead = ((0u - (am + b)) & 15u) >> 2;  // dwords up to the next 16-byte boundary
+    if (lead == 0) tx_store_dwords<0>(a + b, e, ndw);
+    else if (lead == 1) tx_store_dwords<1>(a + b, e, ndw);
+    else if (lead == 2) tx_store_dwords<2>(a + b, e, ndw);
+    else tx_store_dwords<3>(a + b, e, ndw);
+    if (!b) *gptr(reinterpret_cast<uint16_t*>(a + 4 * ndw)) = (uint16_t)(tcp ? d[13] : d[10]);
+}
+
+// One lane's segment: validation (dk_tx_status order), payload sum, header arithmetic, stores.
+struct TxSeg {
+    uint32_t poff, plen, meta, link;
+    uint32_t st;  // dk_tx_status
+    uint32_t H;   // header bytes in front of the payload
+    bool tcp, sum;  // sum: the L4 checksum is computed (its offload flag is off)
+};
+// Before the payload stream: only what the status and the header size need (meta, the link index, the option record
+// of an option-bearing segment). The other descriptor fields are loaded after the stream (tx_seg_finish), so they hold
+// no registers while a step's payload loads are in flight.
+__device__ __forceinline__ void tx_seg_check(const TxSerParams& P, uint32_t i, uint32_t poff, uint32_t plen, TxSeg& S) {
+    const dk_tx_segs& G = P.segs;
+    S.poff = poff;
+    S.plen = plen;
+    S.meta = G.meta[i];
+    S.link = G.link ? G.link[i] : 0u;
+    const uint32_t proto = (S.meta >> 8) & 0xFFu;
+    S.tcp = proto == 6u;
+    S.sum = !(G.flags & (S.tcp ? DK_TX_OFFLOAD_TCP : DK_TX_OFFLOAD_UDP));
+    S.H = 42;
+    S.st = DK_TX_OK;
+    if (proto != 6u && proto != 17u) {
+        S.st = DK_TX_E_PROTO;
+        return;
+    }
+    if (S.tcp) {
+        const uint32_t nib = S.meta >> 28;
+        uint32_t hl = 20;
+        if (nib > 5) {  // the 96-byte record is read for option-bearing segments only
+            hl = G.tcp_opts ? tx_tcp_header_bytes(G.tcp_opts + i) : 0u;
+            if (hl != nib * 4) {
+                S.st = DK_TX_E_OPTS;
+                return;
+            }
+        } else if (nib != 0 && nib != 5) {
+            S.st = DK_TX_E_OPTS;  // a data offset below 5 words has no serialized form
+            return;
+        }
+        S.H = 34 + hl;
+    }
+    if (S.link >= P.nlinks) S.st = DK_TX_E_LINK;
+    else if (S.H + plen > 65535u) S.st = DK_TX_E_LEN;
+    else if (poff < S.H || (uint64_t)poff + plen > P.frames_bytes) S.st = DK_TX_E_RANGE;
+}
+
+__device__ __forceinline__ void tx_seg_finish(const TxSerParams& P, uint32_t i, uint32_t lane, const WaveLds& W,
+                                              const Chunk& C, const TxSeg& S) {
+    const dk_tx_segs& G = P.segs;
+    const bool ok = S.st == DK_TX_OK;
+    __builtin_nontemporal_store(ok ? S.poff - S.H : 0u, gptr(P.off_out) + i);
+    __builtin_nontemporal_store((uint16_t)(ok ? S.H + S.plen : 0u), gptr(P.len_out) + i);
+    if (P.status) __builtin_nontemporal_store(S.st, gptr(P.status) + i);
+    if (!ok) return;
+    const uint32_t src = G.src_ip[i], dst = G.dst_ip[i], ports = G.ports[i];
+    const uint32_t ipw = G.ip_word ? G.ip_word[i] : 0x00FF0000u;  // Ipv4Header::new: identification 0, ttl 255, dscp 0
+    const uint32_t seq = (S.tcp && G.tcp_seq) ? G.tcp_seq[i] : 0u;
+    const uint32_t ack = (S.tcp && G.tcp_ack) ? G.tcp_ack[i] : 0u;
+    const uint32_t winurg = (S.tcp && G.tcp_win) ? G.tcp_win[i] : 0u;
+    uint8_t* a = P.frames + (S.poff - S.H);
+    const uint32_t* lw = reinterpret_cast<const uint32_t*>(P.links + S.link);  // dst_mac[6], src_mac[6], reserved
+    const uint3 L = make_uint3(lw[0], lw[1], lw[2]);
+    const uint32_t proto = S.tcp ? 6u : 17u;
+    const uint32_t tot = S.H - 14 + S.plen, seg = tot - 20;
+    const uint32_t ident = ipw & 0xFFFFu, ttl = (ipw >> 16) & 0xFFu, tos = ipw >> 24;
+    // Ipv4Header::compute_checksum over the 9 words around the checksum field (BE values)
+    const uint32_t ipsum = (0x4500u | tos) + tot + ident + 0x4000u + ((ttl << 8) | proto) + ip_be_sum(src) +
+                           ip_be_sum(dst);
+    const uint32_t ipc = csum_from_residue(mod_ffff(ipsum));
+    const uint32_t sport = ports & 0xFFFFu, dport = ports >> 16;
+    const uint32_t b12 = ((S.H - 34) / 4) << 4 | ((S.meta >> 24) & 1u), b13 = (S.meta >> 16) & 0xFFu;
+    const uint32_t win = winurg & 0xFFFFu, urg = winurg >> 16;
+    uint32_t c = 0;
+    uint32_t optsum = 0;
+    if (S.tcp && S.H > 54) optsum = tx_emit_options(P.segs.tcp_opts + i, a + 54, S.H - 54);
+    if (S.sum) {
+        const uint32_t le = tx_payload_sum(C, W, lane, P.frames + S.poff, S.plen) + optsum;
+        uint32_t be = ip_be_sum(src) + ip_be_sum(dst) + proto + seg + sport + dport;  // pseudo-header, ports
+        be += S.tcp ? be16_sum(seq) + be16_sum(ack) + ((b12 << 8) | b13) + win + urg : seg;
+        c = csum_from_residue(mod_ffff(be_residue(le) + be));
+    }
+    uint32_t d[14];
+    d[0] = L.x;
+    d[1] = L.y;
+    d[2] = L.z;
+    d[3] = 0x0008u | 0x45u << 16 | tos << 24;  // ethertype 0x0800; version 4, IHL 5; dscp << 2 | ecn
+    d[4] = bswap16(tot) | bswap16(ident) << 16;
+    d[5] = 0x0040u | ttl << 16 | proto << 24;  // DF, fragment offset 0
+    d[6] = bswap16(ipc) | (src & 0xFFFFu) << 16;
+    d[7] = (src >> 16) | (dst & 0xFFFFu) << 16;
+    d[8] = (dst >> 16) | bswap16(sport) << 16;
+    const uint32_t sq = __builtin_bswap32(seq), ak = __builtin_bswap32(ack);
+    d[9] = bswap16(dport) | (S.tcp ? sq << 16 : bswap16(seg) << 16);
+    d[10] = S.tcp ? (sq >> 16) | ak << 16 : bswap16(c);
+    d[11] = (ak >> 16) | b12 << 16 | b13 << 24;
+    d[12] = bswap16(win) | bswap16(c) << 16;
+    d[13] = bswap16(urg);
+    tx_store_header(a, d, S.tcp);
+}
+
+__global__ __launch_bounds__(kBlock, DK_MIN_WAVES) void dk_tx_serialize_kernel(TxSerParams P) {
+    __shared__ WaveLds s_wave[kWaves];
+    const uint32_t lane = lane_id();
+    const uint32_t wv = threadIdx.x >> 6;
+    WaveLds& W = s_wave[wv];
+    const WaveRange r = wave_range(P.sched, P.segs.n, wv, lane);
+    uint32_t c, lim, nc, nlim;
+    bool have = r.chunk(0, c, lim);
+    uint32_t noff = 0, nlen = 0;
+    if (have && c + r.lane_off < lim) {
+        noff = P.segs.payload_off[c + r.lane_off];
+        nlen = P.segs.payload_len[c + r.lane_off];
+    }
+    for (uint32_t k = 0; have; k++, c = nc, lim = nlim) {
+        const uint32_t i = c + r.lane_off;
+        const bool live = i < lim;
+        const uint32_t poff = noff, plen = nlen;
+        have = r.chunk(k + 1, nc, nlim);
+        if (have && nc + r.lane_off < nlim) {
+            noff = P.segs.payload_off[nc + r.lane_off];
+            nlen = P.segs.payload_len[nc + r.lane_off];
+        }
+        TxSeg S;
+        S.st = DK_TX_E_PROTO;
+        S.sum = false;
+        if (live) tx_seg_check(P, i, poff, plen, S);
+        // only payloads whose sum is needed are read: failed segments and offloaded checksums load nothing
+        Chunk C;
+        stream_chunk<true, true>(P.frames, P.frames_bytes, live && S.st == DK_TX_OK && S.sum, lane, W, poff, plen, C);
+        if (live) tx_seg_finish(P, i, lane, W, C, S);
+    }
+}
+
 }  // namespace
 }  // namespace dk
 
@@ -2382,5 +2655,18 @@ int dk_launch_tx(const dk::TxParams& p, uint32_t grid, void* stream) {
         hipLaunchKernelGGL(dk::dk_tx_kernel<true>, dim3(grid), dim3(dk::kBlock), 0, s, p);
     else
         hipLaunchKernelGGL(dk::dk_tx_kernel<false>, dim3(grid), dim3(dk::kBlock), 0, s, p);
+    return hipGetLastError() == hipSuccess ? 0 : 5;
+}
+
+int dk_tx_serialize_resident_blocks() {
+    int blocks = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, dk::dk_tx_serialize_kernel, dk::kBlock, 0) != hipSuccess)
+        return 0;
+    return blocks;
+}
+
+int dk_launch_tx_serialize(const dk::TxSerParams& p, uint32_t grid, void* stream) {
+    if (p.segs.n == 0 || grid == 0) return 0;
+    hipLaunchKernelGGL(dk::dk_tx_serialize_kernel, dim3(grid), dim3(dk::kBlock), 0, (hipStream_t)stream, p);
     return hipGetLastError() == hipSuccess ? 0 : 5;
 }

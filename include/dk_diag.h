@@ -59,6 +59,10 @@ int dk_diag_path_stats_read(struct dk_rx_ctx* ctx, uint64_t out[4]); /* synchron
 int dk_diag_rx_set_tuning(struct dk_rx_ctx* ctx, const int32_t* knobs, uint32_t nknobs);
 /* The same for dk_tx_checksum / dk_tx_checksum_fields (process-wide, -1 = the rule). 0. */
 int dk_diag_tx_set_tuning(int32_t split, int32_t sched, int32_t grid_per_cu);
+/* dk_tx_serialize (one kernel, no split form) follows sched and grid_per_cu of the call above; this one caps its grid at
+ * `grid` workgroups in total (process-wide, <= 0 = the rule), so a test can give every wave several chunks of a small
+ * batch. 0. */
+int dk_diag_tx_serialize_set_grid(int32_t grid);
 
 /* Which walk dk_tcp_rx_process runs (dk_tcp.h): walk -1 the engine's rule, 0 one lane per connection, 1 one wave per
  * connection, 2 the relay walk (relay_waves 4 / 8 / 16 waves per connection, else 8), 3 the scan walk. A TCP context

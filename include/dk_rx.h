@@ -298,6 +298,90 @@ int dk_tx_checksum(uint8_t* frames, uint64_t frames_bytes, const uint32_t* off, 
 int dk_tx_checksum_fields(const uint8_t* frames, uint64_t frames_bytes, const uint32_t* off, const uint16_t* len,
                           uint32_t n, uint32_t* fields, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * TX serialize: the inverse of dk_rx_process. One batch call builds the Ethernet / IPv4 / TCP or UDP headers of every
+ * segment in the headroom in front of its payload, bit-exact to the reference's send chain with tx offload on or off:
+ *   TcpHeader::serialize_and_attach   layer4/tcp/header.rs:330-405 (TcpOptions2::serialize :56-101, compute_size
+ *                                     :408-421)  or  UdpHeader::serialize_and_attach  layer4/udp/header.rs:97-130
+ *   Ipv4Header::serialize_and_attach  layer3/ipv4/header.rs:229-266 (constants of Ipv4Header::new :88-104)
+ *   Ethernet2Header::serialize_and_attach  layer2/ethernet2/header.rs:68-73
+ * The output descriptors (off_out, len_out) are those of a dk_rx_batch over the same blob, so a built batch feeds a
+ * NIC ring or dk_rx_process directly. These entry points are additive: DK_RX_ABI_VERSION stays 4 (nothing that
+ * existed changed layout or meaning).
+ * ------------------------------------------------------------------------------------------------------------- */
+/* One L2 next hop: what the ARP cache lookup and the local link address give Ethernet2Header::new
+ * (layer2/mod.rs:85-96). */
+typedef struct dk_tx_link {
+    uint8_t dst_mac[6];
+    uint8_t src_mac[6];
+    uint32_t reserved;
+} dk_tx_link; /* 16 bytes */
+
+/* Per-frame status of dk_tx_serialize. The reference would hit an expect(...) in each failing case; here the frame's
+ * status is set, nothing is written to the blob for it and its off_out / len_out are 0. The first failing check in
+ * this order is the one reported. */
+enum dk_tx_status {
+    DK_TX_OK = 0,
+    DK_TX_E_PROTO = 1, /* ip_protocol is neither 6 nor 17                                                         */
+    DK_TX_E_OPTS = 2,  /* num > 5, unknown kind, SACK with 0 or > 4 blocks (or blocks outside sack[]), TCP header
+                          over 60 bytes, size != data-offset nibble * 4 (a nibble of 1..4 included: no list is
+                          that short), nibble > 5 with tcp_opts == NULL                                           */
+    DK_TX_E_LINK = 3,  /* link[i] >= nlinks                                                                       */
+    DK_TX_E_LEN = 4,   /* H + payload_len > 65535                                                                 */
+    DK_TX_E_RANGE = 5  /* payload_off < H, or payload_off + payload_len > frames_bytes                            */
+};
+
+#define DK_TX_OFFLOAD_TCP 1u /* tcp tx_checksum_offload: TCP checksum bytes written as 0 (tcp/header.rs:401-404) */
+#define DK_TX_OFFLOAD_UDP 2u /* udp checksum_offload: UDP checksum written as 0 (udp/header.rs:123-128)           */
+
+/* Segments to serialize, struct of arrays, device pointers, [n] each. The packing of meta / ports / tcp_win /
+ * tcp_opts is dk_rx_results' own, so receive results can be passed back unchanged. Required: payload_off,
+ * payload_len, meta, src_ip, dst_ip, ports. */
+typedef struct dk_tx_segs {
+    const uint32_t* payload_off; /* byte offset of the payload in the blob                                     */
+    const uint16_t* payload_len;
+    const uint32_t* meta;        /* ip_protocol << 8 | tcp byte 13 << 16 | tcp byte 12 << 24; low byte ignored.
+                                    Of byte 12 the data-offset nibble (0 or 5: no options) and NS (bit 24) are
+                                    used; bits 25-27 are ignored and written as zero                            */
+    const uint32_t* src_ip;
+    const uint32_t* dst_ip;
+    const uint32_t* ports;       /* src_port | dst_port << 16                                                  */
+    const uint32_t* tcp_seq;     /* TCP only; may be NULL when no frame is TCP (NULL reads as 0)               */
+    const uint32_t* tcp_ack;
+    const uint32_t* tcp_win;     /* window | urgent_pointer << 16                                              */
+    const dk_tcp_opts* tcp_opts; /* optional; read only for frames whose meta data-offset nibble is > 5. Entries
+                                    in list order; besides enum dk_tcp_opt_kind, kind 1 (NoOperation, one byte)
+                                    and kind 0 (EndOfOptionsList, zero bytes, as compute_size gives it) are
+                                    accepted on this side. After the list: one EOL byte if it is non-empty, then
+                                    zero padding to a multiple of 4                                             */
+    const uint32_t* ip_word;     /* optional: identification | ttl << 16 | (dscp << 2 | ecn) << 24;
+                                    NULL = Ipv4Header::new's values (0, 255, 0)                                 */
+    const uint32_t* link;        /* optional index into links[]; NULL = links[0] for every frame               */
+    uint32_t n;
+    uint32_t flags;              /* DK_TX_OFFLOAD_*                                                             */
+} dk_tx_segs;
+
+/* Header bytes in front of the payload (14 + 20 + L4 header) for a protocol and an option list (NULL / num 0 = none),
+ * or 0 if the list cannot be serialized (or the protocol is neither 6 nor 17). Pure host function: lets a caller
+ * reserve headroom and fill meta's data-offset nibble ((result - 34) / 4 for TCP). */
+uint32_t dk_tx_header_bytes(uint32_t ip_protocol, const dk_tcp_opts* opts);
+
+/* Serialize the headers of segs->n segments into `frames` on `stream`. Every pointer is a device pointer; the call is
+ * asynchronous and needs no context. For frame i with status DK_TX_OK the H bytes before payload_off[i]
+ * (H = 42 for UDP, 54 + option bytes rounded up to 4 for TCP) are written with exactly the bytes the three reference
+ * functions produce (IPv4: 0x45, DF, fragment offset 0, total_length = H - 14 + payload_len; UDP length =
+ * 8 + payload_len; checksums with the reference's fold, the pseudo-header from the descriptor's src_ip / dst_ip, or 0
+ * under the matching DK_TX_OFFLOAD_* flag), off_out[i] = payload_off[i] - H and len_out[i] = H + payload_len[i]. The
+ * payload is only read; no byte outside [off_out[i], payload_off[i]) is written. What the headroom held before the call
+ * does not matter. `status` ([n] enum dk_tx_status) is optional: NULL = not written.
+ * Caller's contract: a frame's header room [payload_off - H, payload_off) overlaps no other frame's header room or
+ * payload. No slack is needed: a header room may begin at the byte after another frame's payload.
+ * Returns 0, EINVAL (null required pointer, nlinks == 0, frames_bytes > DK_RX_MAX_BLOB) or EIO (launch failure, or no
+ * usable current device: where dk_tx_checksum returns ENODEV, this call keeps to its three values);
+ * n == 0 returns 0 without a launch. */
+int dk_tx_serialize(uint8_t* frames, uint64_t frames_bytes, const dk_tx_segs* segs, const dk_tx_link* links,
+                    uint32_t nlinks, uint32_t* off_out, uint16_t* len_out, uint32_t* status, void* stream);
+
 /* Introspection. */
 const char* dk_rx_verdict_name(int verdict);
 int dk_rx_verdict_errno(int verdict); /* errno the reference returns for this verdict; 0 for deliver/divert/drop */
