@@ -21,7 +21,8 @@ from .rx import (  # noqa: F401
     tx_tuning,
 )
 from .tx import TxSegments, tx_header_bytes, tx_links, tx_serialize  # noqa: F401
+from .tcp_tx import PushList, TcpSender, TcpTxResults, tx_conn_table  # noqa: F401
 
-__all__ = ["Comm", "Config", "Fail", "FrameBatch", "RxEngine", "RxResults", "SocketId", "V", "VERDICTS", "flow_array",
+__all__ = ["PushList", "TcpSender", "TcpTxResults", "tx_conn_table","Comm", "Config", "Fail", "FrameBatch", "RxEngine", "RxResults", "SocketId", "V", "VERDICTS", "flow_array",
            "ipv4", "ipv4_str", "raise_for_verdict", "tx_tuning", "TxSegments", "tx_header_bytes", "tx_links",
            "tx_serialize"]

@@ -167,6 +167,44 @@ TCP_FUNCTIONS = [
                                   c_void_p]),
 ]
 
+# include/dk_tcp.h, TCP send segmentation (dk_tcp_tx_segment)
+TCP_TX_STATUSES = ["SENT", "PARTIAL", "UNSENT", "CLOSED", "E_CONN", "NO_ROOM"]
+(DK_TCP_TX_SENT, DK_TCP_TX_PARTIAL, DK_TCP_TX_UNSENT, DK_TCP_TX_CLOSED, DK_TCP_TX_E_CONN,
+ DK_TCP_TX_NO_ROOM) = range(6)
+TX_CONN_FIELDS = ["state", "snd_una", "snd_nxt", "snd_wnd", "cwnd", "mss", "rcv_nxt", "rcv_wscale", "local_ip",
+                  "remote_ip", "ports", "ip_word", "link", "fin_sent"]
+TX_CONN_DTYPE = np.dtype([(k, "<u4") for k in TX_CONN_FIELDS] +
+                         [("rcv_wnd_hdr", "<u2"), ("reserved0", "<u2"), ("reserved1", "<u4")])
+assert TX_CONN_DTYPE.itemsize == 64
+TCP_TX_RESULT_FIELDS = ["off_out", "len_out", "frame_buf", "sent", "first_frame", "frame_count", "status", "n_frames"]
+
+
+class DkTcpTxConn(ctypes.Structure):
+    _fields_ = [(k, c_uint32) for k in TX_CONN_FIELDS] + [("rcv_wnd_hdr", c_uint16), ("reserved0", c_uint16),
+                                                          ("reserved1", c_uint32)]
+
+
+class DkTcpTxPush(ctypes.Structure):
+    _fields_ = [("conn", c_void_p), ("off", c_void_p), ("len", c_void_p)]
+
+
+class DkTcpTxLayout(ctypes.Structure):
+    _fields_ = [("slot_stride", c_uint32), ("frame_lead", c_uint32)]
+
+
+class DkTcpTxResults(ctypes.Structure):
+    _fields_ = [(name, c_void_p) for name in TCP_TX_RESULT_FIELDS]
+
+
+TCP_TX_FUNCTIONS = [
+    ("dk_tcp_tx_ctx_create", c_int, [c_int32, POINTER(c_void_p)]),
+    ("dk_tcp_tx_ctx_destroy", None, [c_void_p]),
+    ("dk_tcp_tx_frame_bound", c_uint64, [c_void_p, c_uint32, c_uint32]),
+    ("dk_tcp_tx_segment", c_int, [c_void_p, c_void_p, c_uint64, POINTER(DkTcpTxPush), c_uint32, c_void_p, c_uint32,
+                                  c_void_p, c_void_p, c_uint32, c_void_p, c_uint64, POINTER(DkTcpTxLayout), c_uint32,
+                                  c_uint32, POINTER(DkTcpTxResults), c_void_p]),
+]
+
 # include/dk_diag.h (diagnostics, not the receive ABI)
 # include/dk_demi.h: delivered frames as demi_sgarray_t (host-side, no GPU work)
 class DemiSgaseg(ctypes.Structure):
@@ -211,6 +249,7 @@ DIAG_FUNCTIONS = [
     ("dk_diag_rx_set_tuning", c_int, [c_void_p, c_void_p, c_uint32]),
     ("dk_diag_tx_set_tuning", c_int, [c_int32, c_int32, c_int32]),
     ("dk_diag_tx_serialize_set_grid", c_int, [c_int32]),
+    ("dk_diag_tcp_tx_set_grid", c_int, [c_int32]),
     ("dk_diag_tcp_set_walk", c_int, [c_void_p, c_int32, c_int32]),
     ("dk_diag_tcp_last_walk", c_int, [c_void_p]),
     ("dk_diag_tcp_set_sort", c_int, [c_void_p, c_int32]),
@@ -221,7 +260,7 @@ DK_DIAG_RX_KNOBS = ["stage", "split", "small", "sched", "grid", "grid_per_cu", "
 DK_TCP_WALKS = {"lane": 0, "wave": 1, "relay": 2, "scan": 3}
 DK_TCP_SORTS = {"counting": 0, "radix": 1}
 
-ALL_FUNCTIONS = FUNCTIONS + RING_FUNCTIONS + TCP_FUNCTIONS + DIAG_FUNCTIONS + DEMI_FUNCTIONS + COMM_FUNCTIONS
+ALL_FUNCTIONS = FUNCTIONS + RING_FUNCTIONS + TCP_FUNCTIONS + TCP_TX_FUNCTIONS + DIAG_FUNCTIONS + DEMI_FUNCTIONS + COMM_FUNCTIONS
 
 _lib = None
 

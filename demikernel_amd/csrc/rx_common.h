@@ -5,6 +5,7 @@
 
 #include "../../include/dk_diag.h"
 #include "../../include/dk_rx.h"
+#include "../../include/dk_tcp.h"
 
 #if defined(__HIPCC__)
 #define DK_HD __host__ __device__ __forceinline__
@@ -206,6 +207,32 @@ struct TxSerParams {
     uint32_t* status;  // nullable
 };
 
+// TCP send segmentation (dk_tcp_tx_segment, dk_tcp.h): the emit kernel's view of the plan the kernels of
+// tcp_tx_kernels.hip left in the context's scratch.
+struct TcpTxEmitParams {
+    const uint8_t* src;
+    uint8_t* out;
+    uint64_t out_bytes;
+    const uint32_t* conn;  // the push list
+    const uint32_t* off;
+    const uint32_t* len;
+    uint32_t nbufs;
+    const dk_tcp_tx_conn* tx;
+    const dk_tx_link* links;
+    const uint64_t* first;  // [nbufs] exclusive scan of the plan's frame counts
+    const uint64_t* total;  // the frames the plan needs (the capacity test every kernel of the call makes)
+    const uint32_t* rec;    // [nbufs][4], 16-byte aligned: bytes taken, sequence number of the buffer's first byte, ack
+                            // number, header window
+    uint32_t stride, lead, max_frames, flags;
+    uint32_t* off_out;
+    uint16_t* len_out;
+    uint32_t* frame_buf;  // nullable
+};
+// The capacity rule (dk_tcp.h): the plan's frames fit max_frames and their slots fit out_bytes.
+DK_HD bool tcp_tx_fits(uint64_t total, uint32_t max_frames, uint32_t stride, uint64_t out_bytes) {
+    return total <= max_frames && total * stride <= out_bytes;
+}
+
 // TcpHeader::compute_size (tcp/header.rs:408-421) of an option list: 20 + the entries' sizes (TcpOptions2::compute_size
 // :43-54; a SACK entry's blocks must lie inside sack[]) + one EndOfOptionsList byte when the list is not empty, rounded
 // up to 4. 0 when the list cannot be serialized (more than 5 entries, unknown kind, SACK with 0 or > 4 blocks, more
@@ -253,3 +280,5 @@ int dk_tx_resident_blocks();  // occupancy of dk_tx_kernel per CU (0 on error)
 int dk_launch_tx(const dk::TxParams& p, uint32_t grid, void* stream);
 int dk_tx_serialize_resident_blocks();  // occupancy of dk_tx_serialize_kernel per CU (0 on error)
 int dk_launch_tx_serialize(const dk::TxSerParams& p, uint32_t grid, void* stream);
+int dk_tcp_tx_emit_resident_blocks();  // occupancy of dk_tcp_tx_emit_kernel per CU (0 on error)
+int dk_launch_tcp_tx_emit(const dk::TcpTxEmitParams& p, uint32_t grid, void* stream);

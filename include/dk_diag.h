@@ -63,6 +63,8 @@ int dk_diag_tx_set_tuning(int32_t split, int32_t sched, int32_t grid_per_cu);
  * `grid` workgroups in total (process-wide, <= 0 = the rule), so a test can give every wave several chunks of a small
  * batch. 0. */
 int dk_diag_tx_serialize_set_grid(int32_t grid);
+/* The same cap for dk_tcp_tx_segment's emit kernel (dk_tcp.h; process-wide, <= 0 = the rule). 0. */
+int dk_diag_tcp_tx_set_grid(int32_t grid);
 
 /* Which walk dk_tcp_rx_process runs (dk_tcp.h): walk -1 the engine's rule, 0 one lane per connection, 1 one wave per
  * connection, 2 the relay walk (relay_waves 4 / 8 / 16 waves per connection, else 8), 3 the scan walk. A TCP context

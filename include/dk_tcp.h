@@ -15,8 +15,9 @@
  * the end-overlap adjust of the out-of-order store is one byte short (ctrlblk.rs:916), a front-overlapping segment is
  * inserted at the back of the store (ctrlblk.rs:891-899 leave action_index at the end), a FIN-only in-order segment
  * pushes an empty buffer before the EOF buffer (ctrlblk.rs:693 + :1008).
- * Not modelled: the delayed-ACK timer and the ACKs segments trigger, the sender (SND.UNA, RTO, congestion control),
- * states other than ESTABLISHED (FIN-WAIT-1/2 etc.).
+ * Not modelled: the delayed-ACK timer and the ACKs segments trigger, the sender's reaction to ACKs (SND.UNA, RTO,
+ * congestion control; cutting pushed buffers into segments is dk_tcp_tx_segment, below), states other than ESTABLISHED
+ * (FIN-WAIT-1/2 etc.).
  *
  * Conventions as dk_rx.h: 0 or a positive errno; device pointers; asynchronous on the caller's stream. A context holds
  * one set of scratch buffers: calls on one context are serialised — a call on another stream than the previous call
@@ -112,6 +113,125 @@ void dk_tcp_ctx_destroy(dk_tcp_ctx* ctx);
  * misaligned conns) or ENOMEM. */
 int dk_tcp_rx_process(dk_tcp_ctx* ctx, const dk_rx_results* rx, uint32_t n, dk_tcp_conn* conns, uint32_t nconns,
                       const dk_tcp_out* out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * TCP send segmentation: cut the buffers an application pushed into finished TCP frames, for a whole batch of
+ * connections at once. Bit-exact to a loop of Sender::send_segment (tcp/established/sender.rs:124-208) over each
+ * connection's buffers with no ACK arriving meanwhile, the headers from ControlBlock::tcp_header (ctrlblk.rs:699-709:
+ * ACK set, ack_num = RCV.NXT, window = hdr_window_size() :786-803) and the Ethernet / IPv4 / TCP bytes exactly
+ * what dk_tx_serialize writes for the same descriptor (no options: 54 header bytes). For every connection, its
+ * buffers in push order:
+ *   loop: sent = snd_nxt - snd_una (wrapping)
+ *         open = (snd_wnd == 0 || snd_wnd < sent || cwnd < sent) ? 0 : min(snd_wnd - sent, mss, cwnd - sent)
+ *         open == 0 -> the connection stops: the rest of this buffer and every later one stay unsent
+ *         remaining > open -> frame of `open` bytes, flags ACK
+ *         else             -> frame of `remaining` bytes, ACK|PSH (remaining > 0) or ACK|FIN (a zero-length buffer, the
+ *                             end-of-send marker: consumes 1), buffer done
+ *         seq = snd_nxt before the frame; snd_nxt += bytes (or 1)
+ * A sent FIN sets fin_sent; buffers behind a marker, or on a connection whose fin_sent is set, are not sent. The
+ * payload is copied from the source blob into frame slots (a pushed buffer has no headroom between its pieces) and
+ * summed while it is copied: each payload byte is read once and written once.
+ * Not modelled (they stay with the host): the retransmission queue and timers, the RTT estimate, cwnd updates (cwnd is
+ * an input, fixed for the call: CUBIC's decrement of its limited-transmit increase in on_send and its idle restart in
+ * on_cwnd_check_before_send are not applied between the frames of a call), the persist timer.
+ * These entry points are additive: DK_RX_ABI_VERSION stays 4.
+ * ------------------------------------------------------------------------------------------------------------- */
+/* Send side of one connection (Sender + what ControlBlock::tcp_header reads). Device memory, 16-byte aligned, updated
+ * in place (snd_nxt, fin_sent). */
+typedef struct dk_tcp_tx_conn {
+    uint32_t state;       /* enum dk_tcp_state; only DK_TCP_ESTABLISHED sends                                     */
+    uint32_t snd_una;     /* Sender::send_unacked                                                                  */
+    uint32_t snd_nxt;     /* Sender::send_next                                                                     */
+    uint32_t snd_wnd;     /* Sender::send_window                                                                   */
+    uint32_t cwnd;        /* the effective congestion window (cwnd + limited-transmit increase), fixed for the
+                             call; congestion control None: 0xFFFFFFFF                                             */
+    uint32_t mss;         /* 0 never opens the window; above 65,495 (IPv4 total length) is a connection error      */
+    uint32_t rcv_nxt;     /* ack number when no receive table is passed                                            */
+    uint32_t rcv_wscale;  /* receive_window_scale_shift_bits (used with a receive table)                           */
+    uint32_t local_ip;    /* addresses and ports in dk_tx_segs' packing: src = local, dst = remote                 */
+    uint32_t remote_ip;
+    uint32_t ports;       /* local_port | remote_port << 16                                                        */
+    uint32_t ip_word;     /* identification | ttl << 16 | (dscp << 2 | ecn) << 24 (dk_tx_segs.ip_word)             */
+    uint32_t link;        /* index into links[]                                                                    */
+    uint32_t fin_sent;    /* a FIN went out: nothing more is sent                                                  */
+    uint16_t rcv_wnd_hdr; /* header window when no receive table is passed                                         */
+    uint16_t reserved0;
+    uint32_t reserved1;
+} dk_tcp_tx_conn;         /* 64 bytes */
+
+/* The pushed buffers of one call, struct of device arrays, [nbufs] each. conn is non-decreasing: the buffers of one
+ * connection are adjacent and in push order. (off, len) is the buffer's byte range in the source blob; len == 0 is the
+ * end-of-send marker. */
+typedef struct dk_tcp_tx_push {
+    const uint32_t* conn;
+    const uint32_t* off;
+    const uint32_t* len;
+} dk_tcp_tx_push;
+
+/* Where the frames go: frame f of the call starts at out + f * slot_stride + frame_lead and owns slot f, the bytes
+ * [f * slot_stride, (f + 1) * slot_stride) of out. No alignment is required of either value. */
+typedef struct dk_tcp_tx_layout {
+    uint32_t slot_stride;
+    uint32_t frame_lead;
+} dk_tcp_tx_layout;
+
+enum dk_tcp_tx_status {
+    DK_TCP_TX_SENT = 0,    /* the whole buffer (or the FIN) went out                                               */
+    DK_TCP_TX_PARTIAL = 1, /* the window closed inside the buffer: its first `sent` bytes went out                 */
+    DK_TCP_TX_UNSENT = 2,  /* the window was closed before the buffer                                              */
+    DK_TCP_TX_CLOSED = 3,  /* behind an end-of-send marker, or fin_sent was set                                    */
+    DK_TCP_TX_E_CONN = 4,  /* connection-level failure (below): nothing of the connection is sent                  */
+    DK_TCP_TX_NO_ROOM = 5  /* the buffer has frames in the plan, but the call's frames do not fit max_frames /
+                              out_bytes: nothing of the call is sent                                               */
+};
+
+/* Outputs (device). Per frame, [max_frames]: off_out, len_out (a dk_rx_batch over `out`), frame_buf (optional: the
+ * push-list index the frame came from). Per buffer, [nbufs]: sent (sequence space consumed: bytes, or 1 for a FIN),
+ * first_frame, frame_count (the plan's, also when the call ran out of room; saturating at 0xFFFFFFFF), status (enum
+ * dk_tcp_tx_status). n_frames: one word, the frames the plan needs (saturating at 0xFFFFFFFF). */
+typedef struct dk_tcp_tx_results {
+    uint32_t* off_out;
+    uint16_t* len_out;
+    uint32_t* frame_buf;
+    uint32_t* sent;
+    uint32_t* first_frame;
+    uint32_t* frame_count;
+    uint32_t* status;
+    uint32_t* n_frames;
+} dk_tcp_tx_results;
+
+typedef struct dk_tcp_tx_ctx dk_tcp_tx_ctx;
+
+/* Scratch (scan buffers, the per-buffer plan) for dk_tcp_tx_segment on `device`; calls on one context are serialised
+ * as dk_tcp_ctx's are. Returns 0, EINVAL or ENOMEM. */
+int dk_tcp_tx_ctx_create(int32_t device, dk_tcp_tx_ctx** out);
+void dk_tcp_tx_ctx_destroy(dk_tcp_tx_ctx* ctx);
+
+/* Upper bound of the frames a push list can need, from host-side lengths: the sum of max(1, ceil(len / mss)) (0 when
+ * mss == 0: nothing is ever sent). Pure host function. */
+uint64_t dk_tcp_tx_frame_bound(const uint32_t* len, uint32_t nbufs, uint32_t mss);
+
+/* Cut push->*[0 .. nbufs) (ranges of src[0 .. src_bytes), only read) into frames in out[0 .. out_bytes), asynchronously
+ * on `stream`. tx_conns[0 .. nconns) is updated in place. Header fields: with rx_conns (the dk_tcp_conn table of the same
+ * connections, e.g. as dk_tcp_rx_process just left it on this stream) ack = rx_conns[c].receive_next and window =
+ * (buffer_size - (receive_next - reader_next)) >> rcv_wscale; with rx_conns == NULL they are rcv_nxt and rcv_wnd_hdr.
+ * The TCP checksum is computed over the copied payload, or written as 0 under DK_TX_OFFLOAD_TCP in `flags`.
+ * Frames are numbered in push-list order, so a connection's frames are consecutive and in sequence order. No byte of
+ * out outside the frames is written. src and out must not overlap.
+ * Connection-level failures (every buffer of the connection gets DK_TCP_TX_E_CONN, its state is untouched): conn index
+ * >= nconns, state != ESTABLISHED, a window that does not fit 16 bits (hdr_window_size would panic), link >= nlinks,
+ * frame_lead + 54 + mss > slot_stride, mss > 65,495, a buffer range outside src_bytes.
+ * Capacity is all or nothing: n_frames always reports the frames the plan needs; if that exceeds max_frames, or
+ * n_frames * slot_stride exceeds out_bytes, no frame is written, no connection is updated, `sent` is 0 everywhere and
+ * the buffers that had frames report DK_TCP_TX_NO_ROOM; the caller retries with more room. The test is made on the
+ * device: there is no host round trip.
+ * Returns 0, EINVAL (null required pointer, misaligned tx_conns, src_bytes or out_bytes > DK_RX_MAX_BLOB, nlinks == 0),
+ * ENOMEM or EIO. */
+int dk_tcp_tx_segment(dk_tcp_tx_ctx* ctx, const uint8_t* src, uint64_t src_bytes, const dk_tcp_tx_push* push,
+                      uint32_t nbufs, dk_tcp_tx_conn* tx_conns, uint32_t nconns, const dk_tcp_conn* rx_conns,
+                      const dk_tx_link* links, uint32_t nlinks, uint8_t* out, uint64_t out_bytes,
+                      const dk_tcp_tx_layout* layout, uint32_t max_frames, uint32_t flags,
+                      const dk_tcp_tx_results* results, void* stream);
 
 #ifdef __cplusplus
 }
