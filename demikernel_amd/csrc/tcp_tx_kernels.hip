@@ -36,7 +36,7 @@ namespace {
 constexpr int kBlock = 256;
 constexpr uint32_t kItems = 4;                 // consecutive items per thread
 constexpr uint32_t kTile = kBlock * kItems;    // items per workgroup of a scan
-constexpr uint32_t kMaxMss = 65495;            // 40 + mss must fit the IPv4 total length
+constexpr uint32_t kMaxMss = 65481;            // 54 + mss, the frame, must fit len_out / dk_rx_batch.len (16 bits)
 constexpr uint32_t kCommit = 1u, kCommitFin = 2u;
 
 struct Plan {

@@ -145,7 +145,8 @@ typedef struct dk_tcp_tx_conn {
     uint32_t snd_wnd;     /* Sender::send_window                                                                   */
     uint32_t cwnd;        /* the effective congestion window (cwnd + limited-transmit increase), fixed for the
                              call; congestion control None: 0xFFFFFFFF                                             */
-    uint32_t mss;         /* 0 never opens the window; above 65,495 (IPv4 total length) is a connection error      */
+    uint32_t mss;         /* 0 never opens the window; above 65,481 (54 + mss must fit len_out) is a connection
+                             error                                                                                 */
     uint32_t rcv_nxt;     /* ack number when no receive table is passed                                            */
     uint32_t rcv_wscale;  /* receive_window_scale_shift_bits (used with a receive table)                           */
     uint32_t local_ip;    /* addresses and ports in dk_tx_segs' packing: src = local, dst = remote                 */
@@ -220,7 +221,8 @@ uint64_t dk_tcp_tx_frame_bound(const uint32_t* len, uint32_t nbufs, uint32_t mss
  * out outside the frames is written. src and out must not overlap.
  * Connection-level failures (every buffer of the connection gets DK_TCP_TX_E_CONN, its state is untouched): conn index
  * >= nconns, state != ESTABLISHED, a window that does not fit 16 bits (hdr_window_size would panic), link >= nlinks,
- * frame_lead + 54 + mss > slot_stride, mss > 65,495, a buffer range outside src_bytes.
+ * frame_lead + 54 + mss > slot_stride, mss > 65,481 (the frame of 54 + mss bytes, not the IPv4 datagram, is what the
+ * 16-bit len_out and dk_rx_batch.len must hold), a buffer range outside src_bytes.
  * Capacity is all or nothing: n_frames always reports the frames the plan needs; if that exceeds max_frames, or
  * n_frames * slot_stride exceeds out_bytes, no frame is written, no connection is updated, `sent` is 0 everywhere and
  * the buffers that had frames report DK_TCP_TX_NO_ROOM; the caller retries with more room. The test is made on the

@@ -19,7 +19,7 @@ SENT, PARTIAL, UNSENT, CLOSED, E_CONN, NO_ROOM = range(6)
 ESTABLISHED = 1
 FIN, PSH, ACK = 0x01, 0x08, 0x10
 M32 = 0xFFFFFFFF
-MAX_MSS = 65495
+MAX_MSS = 65481  # 54 + mss, the whole frame, must fit the 16-bit len_out (dk_rx_batch.len)
 
 
 def open_window(snd_una: int, snd_nxt: int, snd_wnd: int, cwnd: int, mss: int) -> int:
