@@ -11,6 +11,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import demux_keys as DK
 from demikernel_amd import _native as N
 from demikernel_amd import ring as RG
 from demikernel_amd import synth
@@ -284,49 +285,9 @@ M32 = 0xFFFFFFFF
 ACTIVE = N.DK_FLOW_TCP_ACTIVE
 
 
-def _flow_hash(kind, lip, rip, ports):  # rx_common.h flow_hash
-    h = (kind * 0x9E3779B1) & M32
-    h ^= lip
-    h = (h * 0x85EBCA6B) & M32
-    h ^= h >> 13
-    h ^= rip
-    h = (h * 0xC2B2AE35) & M32
-    h ^= h >> 16
-    h ^= ports
-    h = (h * 0x27D4EB2F) & M32
-    h ^= h >> 15
-    return h
-
-
-def _h2(kind, lip, rip):  # flow_hash's state just before `ports` is mixed in (the rest is a bijection of h2 ^ ports)
-    h = (kind * 0x9E3779B1) & M32
-    h ^= lip
-    h = (h * 0x85EBCA6B) & M32
-    h ^= h >> 13
-    h ^= rip
-    h = (h * 0xC2B2AE35) & M32
-    h ^= h >> 16
-    return h
-
-
-def _fmix(h):
-    h ^= h >> 16
-    h = (h * 0x85EBCA6B) & M32
-    h ^= h >> 13
-    h = (h * 0xC2B2AE35) & M32
-    h ^= h >> 16
-    return h
-
-
-def _mulhi(a, b):
-    return (int(a) * int(b)) >> 32
-
-
-def _lt_lookup(words, n, nb, lip, rip, ports):  # rx_kernels.hip lt_lookup, on the host
-    h = _flow_hash(ACTIVE, lip, rip, ports)
-    d = int(words[3 * n + _mulhi(h, nb)])
-    sl = _mulhi(_fmix(h ^ ((d * 0x9E3779B1 + 0x7F4A7C15) & M32)), n)
-    return int(words[2 * n + sl]) if int(words[sl]) == rip and int(words[n + sl]) == ports else None
+# the hashes and lookups of rx_common.h restated in Python: tests/demux_keys.py
+_flow_hash, _h2, _fmix, _mulhi, _lt_lookup = DK.flow_hash, DK.h2, DK.fmix32, DK.mulhi, DK.lt_lookup
+_ub_hash, _ub_lookup = DK.ub_hash, DK.ub_lookup
 
 
 def _ltable(driver, tmp_path, keys, cfg_ip, other=()):
@@ -378,25 +339,6 @@ def test_lds_table_builder(driver, tmp_path):
     assert _ltable(driver, tmp_path, [(r1, p1, 1), (r1, p1, 2)], cfg)[0] == 0  # duplicated key
 
 
-def _ub_hash(port, seed):
-    h = (port * 0x9E3779B1 + seed) & 0xFFFFFFFF
-    h ^= h >> 16
-    h = (h * 0x85EBCA6B) & 0xFFFFFFFF
-    h ^= h >> 13
-    h = (h * 0xC2B2AE35) & 0xFFFFFFFF
-    return h ^ (h >> 16)
-
-
-def _ub_lookup(words, mask, seed, port):
-    """rx_common.h ub_pick over the words of the port's two buckets."""
-    h = _ub_hash(port, seed)
-    b1, b2 = h & mask, (h >> 16) & mask
-    for e in (int(words[2 * b1]), int(words[2 * b1 + 1]), int(words[2 * b2]), int(words[2 * b2 + 1])):
-        if (e ^ port) & 0xFFFF == 0 and e >> 16 != 0xFFFF:
-            return e >> 16
-    return None
-
-
 def test_udp_bind_table_builder(driver, tmp_path):
     """The compact UDP bind table (rx_common.h, lds_table.h build_udp_table: two-word buckets, load <= 1/2) from
     port-table words: 1..32,768 binds on consecutive and random ports (ports 0 and 65535 included), every bind found at
@@ -434,3 +376,39 @@ def test_udp_bind_table_builder(driver, tmp_path):
     local = np.full(65536, none, np.uint32)
     local[80] = 0xFFFF
     assert build(local)[0] == 0
+
+
+# --- the crafted tables of tests/demux_keys.py through the real builders ------------------------------------------
+def _ltable_slots(driver, tmp_path, slots, cfg_ip):
+    """build_lds_table over the given open-addressing slots (u32[cap][4]) as they are."""
+    cap = len(slots)
+    out = run(driver, "ltable", np.array([cap, cfg_ip], np.uint32).tobytes() + slots.tobytes(), tmp_path)
+    ok, n, nb, nw = np.frombuffer(out[:16], np.int32)
+    return int(ok), int(n), int(nb), np.frombuffer(out[16:16 + 4 * nw], np.uint32)
+
+
+@pytest.mark.parametrize("name", DK.CASES)
+def test_crafted_tables_host_builders_agree(driver, tmp_path, name):
+    """Both host builders (lds_table.h) on every crafted table, from the restated open-addressing slots and port-table
+    words: refused exactly where the restatement refuses (one_hash: eight keys with one hash; udp_fid_edge at flow id
+    0xFFFF), and otherwise the same key and bucket counts, the same words (crowded_bucket: a displacement word of
+    65,536 or more), the same mask and seed (udp_seed: seed 3 after 0, 1 and 2 fail)."""
+    t = DK.tables(name)
+    ok, n, nb, words = _ltable_slots(driver, tmp_path, DK.slot_words(t.slots), DK.CFG)
+    assert bool(ok) == (t.lds is not None), name
+    if name == "one_hash":
+        assert not ok
+    if t.lds is not None:
+        assert (n, nb) == (t.lds.n, t.lds.nb) and np.array_equal(words, t.lds.words), name
+        assert words[3 * n: 3 * n + nb].tolist() == t.lds.disp
+        if name == "crowded_bucket":
+            assert int(words[3 * n]) >= 65536
+    out = run(driver, "utable", DK.udp_local_words(DK.case(name).flows).tobytes(), tmp_path)
+    ok, mask, seed, _ = (int(x) for x in np.frombuffer(out[:16], np.uint32))
+    assert bool(ok) == (t.ub is not None), name
+    if t.ub is not None:
+        assert (mask, seed) == (t.ub.mask, t.ub.seed) and np.array_equal(np.frombuffer(out[16:], np.uint32), t.ub.words)
+    if name == "udp_seed":
+        assert ok and (mask, seed) == (15, 3)
+    if name in ("udp_fid_edge_fffe", "udp_fid_edge_ffff"):
+        assert ok == (name == "udp_fid_edge_fffe")
