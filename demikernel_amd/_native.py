@@ -167,6 +167,37 @@ TCP_FUNCTIONS = [
                                   c_void_p]),
 ]
 
+# include/dk_tcp.h, the sender's reaction to ACKs (dk_tcp_ack_process)
+DK_TCP_TX_TIME_NONE = 0xFFFFFFFFFFFFFFFF
+TCP_ACK_STATUSES = ["OK", "E_STATE", "E_SND_NXT", "E_FLIGHT", "E_WSCALE", "E_WL2", "E_QUEUE", "E_DRY"]
+ACK_CONN_DTYPE = np.dtype([("wl1", "<u4"), ("wl2", "<u4"), ("snd_wscale", "<u4"), ("received_sample", "<u4"),
+                           ("q_first", "<u4"), ("q_count", "<u4"), ("rtx_armed", "<u4"), ("reserved", "<u4"),
+                           ("srtt", "<f8"), ("rttvar", "<f8"), ("rto", "<f8"), ("rtx_base_ns", "<u8")])
+assert ACK_CONN_DTYPE.itemsize == 64
+TCP_ACK_OUT_FIELDS = ["acked", "status", "new_acks", "dup_acks", "bytes_acked", "samples"]
+
+
+class DkTcpAckConn(ctypes.Structure):
+    _fields_ = [("wl1", c_uint32), ("wl2", c_uint32), ("snd_wscale", c_uint32), ("received_sample", c_uint32),
+                ("q_first", c_uint32), ("q_count", c_uint32), ("rtx_armed", c_uint32), ("reserved", c_uint32),
+                ("srtt", ctypes.c_double), ("rttvar", ctypes.c_double), ("rto", ctypes.c_double),
+                ("rtx_base_ns", c_uint64)]
+
+
+class DkTcpUnacked(ctypes.Structure):
+    _fields_ = [("off", c_void_p), ("len", c_void_p), ("tx_time", c_void_p)]
+
+
+class DkTcpAckOut(ctypes.Structure):
+    _fields_ = [(name, c_void_p) for name in TCP_ACK_OUT_FIELDS]
+
+
+TCP_ACK_FUNCTIONS = [
+    ("dk_tcp_ack_process", c_int, [c_void_p, POINTER(DkRxResults), c_uint32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_uint32, POINTER(DkTcpUnacked), c_uint32, c_uint64, POINTER(DkTcpAckOut),
+                                   c_void_p]),
+]
+
 # include/dk_tcp.h, TCP send segmentation (dk_tcp_tx_segment)
 TCP_TX_STATUSES = ["SENT", "PARTIAL", "UNSENT", "CLOSED", "E_CONN", "NO_ROOM"]
 (DK_TCP_TX_SENT, DK_TCP_TX_PARTIAL, DK_TCP_TX_UNSENT, DK_TCP_TX_CLOSED, DK_TCP_TX_E_CONN,
@@ -254,13 +285,17 @@ DIAG_FUNCTIONS = [
     ("dk_diag_tcp_last_walk", c_int, [c_void_p]),
     ("dk_diag_tcp_set_sort", c_int, [c_void_p, c_int32]),
     ("dk_diag_tcp_last_sort", c_int, [c_void_p]),
+    ("dk_diag_tcp_ack_set_form", c_int, [c_void_p, c_int32]),
+    ("dk_diag_tcp_ack_last_form", c_int, [c_void_p]),
 ]
 DK_DIAG_RX_KNOBS = ["stage", "split", "small", "sched", "grid", "grid_per_cu", "debug", "lds_table", "tail", "udp_table",
                     "host_zc"]
 DK_TCP_WALKS = {"lane": 0, "wave": 1, "relay": 2, "scan": 3}
 DK_TCP_SORTS = {"counting": 0, "radix": 1}
+DK_TCP_ACK_FORMS = {"lane": 0, "wave": 1, "chip": 2}
 
-ALL_FUNCTIONS = FUNCTIONS + RING_FUNCTIONS + TCP_FUNCTIONS + TCP_TX_FUNCTIONS + DIAG_FUNCTIONS + DEMI_FUNCTIONS + COMM_FUNCTIONS
+ALL_FUNCTIONS = (FUNCTIONS + RING_FUNCTIONS + TCP_FUNCTIONS + TCP_ACK_FUNCTIONS + TCP_TX_FUNCTIONS + DIAG_FUNCTIONS +
+                 DEMI_FUNCTIONS + COMM_FUNCTIONS)
 
 _lib = None
 

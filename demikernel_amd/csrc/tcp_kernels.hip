@@ -41,6 +41,7 @@
 
 #include "../../include/dk_diag.h"
 #include "../../include/dk_tcp.h"
+#include "tcp_order.h"
 
 namespace dk_tcp {
 namespace {
@@ -1767,7 +1768,18 @@ struct dk_tcp_ctx {
     int last_walk = -1;                   // the walk the last call ran (dk_diag_tcp_last_walk)
     int sort = -1;                        // dk_diag_tcp_set_sort: 1 the radix sort always, -1 the rule
     int last_sort = -1;                   // the sort the last call ran (dk_diag_tcp_last_sort)
+    // what the last call leaves for dk_tcp_ack_process (tcp_order.h): its n, nconns and number, and that call's state
+    bool ord_live = false;
+    uint32_t ord_n = 0, ord_nconns = 0, ord_call = 0;
+    dk_tcp_ack_state ack;
 };
+
+int dk_tcp_ctx_order(dk_tcp_ctx* t, dk_tcp_order* o) {
+    if (!t || !o) return EINVAL;
+    *o = dk_tcp_order{t->device, t->svals, t->range, t->rec, t->ord_live, t->ord_n, t->ord_nconns, t->ord_call,
+                      t->last, &t->last_stream, &t->used, &t->ack};
+    return 0;
+}
 
 extern "C" {
 
@@ -1823,7 +1835,7 @@ void dk_tcp_ctx_destroy(dk_tcp_ctx* t) {
     for (void* p : {(void*)t->keys, (void*)t->skeys, (void*)t->svals, (void*)t->range, (void*)t->rec, (void*)t->temp,
                     (void*)t->cls, (void*)t->open_until, (void*)t->scan_sum, (void*)t->scan_post, (void*)t->scan_ends,
                     (void*)t->scan_idx, (void*)t->scan_rec,
-                    (void*)t->scan_head, (void*)t->shape, (void*)t->csort})
+                    (void*)t->scan_head, (void*)t->shape, (void*)t->csort, t->ack.scratch})
         if (p) (void)hipFree(p);
     if (t->shape_host) (void)hipHostFree(const_cast<uint32_t*>(t->shape_host));
     (void)hipEventDestroy(t->last);
@@ -1841,8 +1853,10 @@ int dk_tcp_rx_process(dk_tcp_ctx* t, const dk_rx_results* rx, uint32_t n, dk_tcp
     if (n > 0x7FFFFFFFu || nconns > 0x7FFFFFFFu ||
         (uint64_t)n + (uint64_t)DK_TCP_DELIV_EXTRA * nconns > 0xFFFFFFFFull)
         return EINVAL;
+    t->ord_live = false;
     if (n == 0 && nconns == 0) {
         t->last_sort = -1;
+        t->ord_live = true, t->ord_n = 0, t->ord_nconns = 0, t->ord_call++;
         return 0;
     }
     DeviceGuard g(t->device);
@@ -1986,6 +2000,7 @@ int dk_tcp_rx_process(dk_tcp_ctx* t, const dk_rx_results* rx, uint32_t n, dk_tcp
     if (hipEventRecord(t->last, s) != hipSuccess) return EINVAL;
     t->last_stream = s;
     t->used = true;
+    t->ord_live = true, t->ord_n = n, t->ord_nconns = nconns, t->ord_call++;
     return 0;
 }
 

@@ -1,0 +1,41 @@
+// tcp_order.h — what a dk_tcp_rx_process call leaves in its context for the call that follows it on the same batch
+// (dk_tcp_ack_process, tcp_ack_kernels.hip): the batch's order by connection, still in the context's scratch, and the
+// context's serialisation state. Internal to libdk_rx.so.
+#ifndef DK_TCP_ORDER_H
+#define DK_TCP_ORDER_H
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+struct dk_tcp_ctx;
+
+struct dk_tcp_ack_state {
+    int form = -1;       // dk_diag_tcp_ack_set_form: 0 lane, 1 wave, 2 chip, -1 the rule
+    int last_form = -1;  // the form the last dk_tcp_ack_process call ran
+    uint32_t done = 0;   // the dk_tcp_rx_process call number the last dk_tcp_ack_process call consumed
+    void* scratch = nullptr;  // the chip form's per-window arrays (device; freed by dk_tcp_ctx_destroy)
+    size_t scratch_cap = 0;
+};
+
+struct dk_tcp_order {
+    int device;
+    // connection c's walked segments are the frames svals[range[2c] .. range[2c + 1]), in arrival order (the segments
+    // the key kernel classified, which never reach process_ack, follow up to range[2c + 2]); rec[i] = {seq, ack, meta,
+    // payload} of frame i
+    const uint32_t* svals;
+    const uint32_t* range;
+    const uint4* rec;
+    bool live;              // the last dk_tcp_rx_process call completed its launches: the three arrays are its
+    uint32_t n, nconns;     // that call's
+    uint32_t call;          // its number on this context (from 1)
+    hipEvent_t last;        // the context's serialisation (tcp_kernels.hip, struct dk_tcp_ctx)
+    hipStream_t* last_stream;
+    bool* used;
+    dk_tcp_ack_state* ack;
+};
+
+// 0, or EINVAL for a null context.
+int dk_tcp_ctx_order(dk_tcp_ctx* ctx, dk_tcp_order* out);
+
+#endif  // DK_TCP_ORDER_H

@@ -79,6 +79,13 @@ int dk_diag_tcp_set_sort(struct dk_tcp_ctx* ctx, int32_t sort);
 /* The sort the context's last dk_tcp_rx_process call ordered its batch with (0 the counting pass, 1 the radix sort;
  * -1 none yet, or a call with no segments or no table rows, which orders nothing by connection). */
 int dk_diag_tcp_last_sort(const struct dk_tcp_ctx* ctx);
+/* Which form dk_tcp_ack_process runs (dk_tcp.h): form -1 the engine's rule, 0 one lane per connection, 1 one wave per
+ * connection, 2 the chip form (the segments' windows across the chip, one wave per connection for the rest). 0 or
+ * EINVAL. */
+int dk_diag_tcp_ack_set_form(struct dk_tcp_ctx* ctx, int32_t form);
+/* The form the context's last dk_tcp_ack_process call ran (0 lane, 1 wave, 2 chip; -1 none yet, or a call with no
+ * table rows). */
+int dk_diag_tcp_ack_last_form(const struct dk_tcp_ctx* ctx);
 
 #ifdef __cplusplus
 }

@@ -15,9 +15,12 @@
  * the end-overlap adjust of the out-of-order store is one byte short (ctrlblk.rs:916), a front-overlapping segment is
  * inserted at the back of the store (ctrlblk.rs:891-899 leave action_index at the end), a FIN-only in-order segment
  * pushes an empty buffer before the EOF buffer (ctrlblk.rs:693 + :1008).
- * Not modelled: the delayed-ACK timer and the ACKs segments trigger, the sender's reaction to ACKs (SND.UNA, RTO,
- * congestion control; cutting pushed buffers into segments is dk_tcp_tx_segment, below), states other than ESTABLISHED
- * (FIN-WAIT-1/2 etc.).
+ * The sender's reaction to the ACKs those segments carry (SND.UNA, the send window, the unacknowledged queue, the RTT
+ * estimate and the retransmit deadline) is dk_tcp_ack_process and cutting pushed buffers into segments is
+ * dk_tcp_tx_segment, both below.
+ * Not modelled: the delayed-ACK timer and the ACKs segments trigger, congestion control (on_ack_received: the host
+ * replays it from dk_tcp_ack_out), the retransmit timer's firing and retransmit() itself, states other than
+ * ESTABLISHED (FIN-WAIT-1/2 etc.).
  *
  * Conventions as dk_rx.h: 0 or a positive errno; device pointers; asynchronous on the caller's stream. A context holds
  * one set of scratch buffers: calls on one context are serialised — a call on another stream than the previous call
@@ -131,9 +134,10 @@ int dk_tcp_rx_process(dk_tcp_ctx* ctx, const dk_rx_results* rx, uint32_t n, dk_t
  * A sent FIN sets fin_sent; buffers behind a marker, or on a connection whose fin_sent is set, are not sent. The
  * payload is copied from the source blob into frame slots (a pushed buffer has no headroom between its pieces) and
  * summed while it is copied: each payload byte is read once and written once.
- * Not modelled (they stay with the host): the retransmission queue and timers, the RTT estimate, cwnd updates (cwnd is
- * an input, fixed for the call: CUBIC's decrement of its limited-transmit increase in on_send and its idle restart in
- * on_cwnd_check_before_send are not applied between the frames of a call), the persist timer.
+ * Not modelled (they stay with the host): retransmission and the timers' firing, cwnd updates (cwnd is an input, fixed
+ * for the call: CUBIC's decrement of its limited-transmit increase in on_send and its idle restart in
+ * on_cwnd_check_before_send are not applied between the frames of a call), the persist timer. The unacknowledged queue
+ * and the RTT estimate are dk_tcp_ack_process's (below).
  * These entry points are additive: DK_RX_ABI_VERSION stays 4.
  * ------------------------------------------------------------------------------------------------------------- */
 /* Send side of one connection (Sender + what ControlBlock::tcp_header reads). Device memory, 16-byte aligned, updated
@@ -234,6 +238,96 @@ int dk_tcp_tx_segment(dk_tcp_tx_ctx* ctx, const uint8_t* src, uint64_t src_bytes
                       const dk_tx_link* links, uint32_t nlinks, uint8_t* out, uint64_t out_bytes,
                       const dk_tcp_tx_layout* layout, uint32_t max_frames, uint32_t flags,
                       const dk_tcp_tx_results* results, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * The sender's reaction to ACKs: what ControlBlock::process_ack (ctrlblk.rs:607-650) hands to Sender::process_ack
+ * (sender.rs:406-474, with update_retransmit_deadline :476-488, update_send_window :490-508 and
+ * RtoCalculator::add_sample / update_rto, rto.rs:40-79, in f64), for every connection of a batch at once. The
+ * segments that reach it are those dk_tcp_rx_process gave DELIVERED, STORED, STORE_DUP, NO_DATA or FIN, in arrival
+ * order within their connection. With una = snd_una, per such segment (seq, ack, win = the raw header window):
+ *   acked = ack - una (wrapping; 0 = a duplicate ACK, >= 2^31 = an old one)
+ *   ack == una: dup_acks += 1
+ *   una <seq ack (a new ACK): new_acks += 1; pop ack - una bytes from the unacknowledged queue; una = ack;
+ *       if wl1 <seq seq or (wl1 == seq and wl2 <=seq ack): snd_wnd = win << snd_wscale, wl1 = seq, wl2 = ack;
+ *       the retransmit deadline follows the queue's front.
+ * The unacknowledged queue of connection c is pool[q_first .. q_first + q_count): entries {off, len, tx_time}, len == 0
+ * the end-of-send marker, tx_time in nanoseconds or DK_TCP_TX_TIME_NONE (retransmitted, or trimmed: Karn). Popping r
+ * bytes, while r != 0, takes the front entry: tx_time != NONE adds the sample now - tx_time (saturating at 0) to the
+ * RTO state; len > r trims it (off += r, len -= r, tx_time = NONE) and stops; the marker ends the pop (r = 0) and
+ * leaves the queue; otherwise r -= len and the entry leaves the queue. `now_ns` is one value per call. After a new
+ * ACK rtx_armed = the queue is not empty and rtx_base_ns = the front's tx_time (now_ns when that is NONE, 0 when the
+ * queue is empty); the host adds rto (the Duration conversion stays there). srtt, rttvar and rto are the
+ * reference's f64 values bit for bit: rtt = (double)(d / 10^9) + (double)(d % 10^9) / 1e9; the first sample sets
+ * srtt = rtt, rttvar = rtt / 2; later ones rttvar = 0.75 rttvar + 0.25 |srtt - rtt|, then srtt = 0.875 srtt + 0.125
+ * rtt; rto = clamp(srtt + max(0.001, 4 rttvar), 0.1, 60.0), no operation contracted.
+ * One deviation: an ack at wrapping distance exactly 2^31 behind a una that equals snd_nxt compares as new in the
+ * reference, which then spins on the empty queue; here it is an old ACK (acked = 2^31, no effect).
+ * Congestion control stays with the host: acked[] in arrival order with new_acks / dup_acks is what on_ack_received
+ * needs.
+ * ------------------------------------------------------------------------------------------------------------- */
+#define DK_TCP_TX_TIME_NONE (~0ull)
+
+/* The sender state dk_tcp_tx_conn does not hold, indexed by flow id. Device memory, 16-byte aligned, updated in
+ * place. */
+typedef struct dk_tcp_ack_conn {
+    uint32_t wl1, wl2;         /* SND.WL1 / SND.WL2: send_window_last_update_seq / _ack                            */
+    uint32_t snd_wscale;       /* send_window_scale_shift_bits                                                     */
+    uint32_t received_sample;  /* RtoCalculator::received_sample                                                   */
+    uint32_t q_first, q_count; /* the connection's entries: pool[q_first .. q_first + q_count)                     */
+    uint32_t rtx_armed;        /* retransmit_deadline_time_secs is Some                                            */
+    uint32_t reserved;
+    double srtt, rttvar, rto;  /* RtoCalculator's state (new(): 1.0, 0.0, 1.0)                                      */
+    uint64_t rtx_base_ns;      /* the deadline is rtx_base_ns + rto                                                */
+} dk_tcp_ack_conn;             /* 64 bytes */
+
+/* The pool of unacknowledged-queue entries, struct of device arrays, [nq] each. */
+typedef struct dk_tcp_unacked {
+    uint32_t* off;
+    uint32_t* len;
+    uint64_t* tx_time;
+} dk_tcp_unacked;
+
+enum dk_tcp_ack_status {
+    DK_TCP_ACK_OK = 0,
+    DK_TCP_ACK_E_STATE = 1,    /* tx_conns[c].state != DK_TCP_ESTABLISHED                                          */
+    DK_TCP_ACK_E_SND_NXT = 2,  /* rx_conns[c].send_next != tx_conns[c].snd_nxt: the walk judged ack <= SND.NXT
+                                  against the former                                                               */
+    DK_TCP_ACK_E_FLIGHT = 3,   /* snd_nxt - snd_una >= 2^31                                                        */
+    DK_TCP_ACK_E_WSCALE = 4,   /* snd_wscale > 14                                                                  */
+    DK_TCP_ACK_E_WL2 = 5,      /* wl2 ahead of snd_una ((int32_t)(wl2 - snd_una) > 0)                              */
+    DK_TCP_ACK_E_QUEUE = 6,    /* q_first + q_count beyond the pool                                                */
+    DK_TCP_ACK_E_DRY = 7       /* the queue ran dry before the acknowledged bytes were consumed                    */
+};
+
+/* Outputs (device). acked: [n], per frame, 0 for frames that are not ACK-processed. Per connection, [nconns]: status
+ * (enum dk_tcp_ack_status), new_acks, dup_acks, bytes_acked (SND.UNA's advance), samples (RTT samples taken). A
+ * connection-level failure leaves the connection's state and queue untouched, acked 0 for its segments and its
+ * counts 0. */
+typedef struct dk_tcp_ack_out {
+    uint32_t* acked;
+    uint32_t* status;
+    uint32_t* new_acks;
+    uint32_t* dup_acks;
+    uint32_t* bytes_acked;
+    uint32_t* samples;
+} dk_tcp_ack_out;
+
+/* Follows the dk_tcp_rx_process call of the same ctx, with that call's rx, n and nconns, `action` that call's
+ * dk_tcp_out.action and rx_conns its table, with no other call on the context between them: it reuses that call's
+ * per-connection arrival order, which is still in the context's scratch. Asynchronous on `stream`, serialised with the
+ * context's other calls as they are. Writes snd_una and snd_wnd of tx_conns, the ack_conns entries, the pool entry at
+ * each queue's front, and `out`; nothing else. The engine runs one lane per connection; one wave per connection at
+ * >= 8 segments per connection; at >= 1,024 segments per connection and <= 256 connections the chip form (each
+ * 64-segment window's part computed across the chip, one wave per connection for the scan over the windows, the queue
+ * and the commit). In the two parallel forms a connection whose wl1 / wl2 / sequence numbers do not allow their ordering
+ * argument, or whose pop meets a marker anywhere but as its last byte, is redone by one lane;
+ * dk_diag_tcp_ack_set_form (dk_diag.h) forces a form. Results are identical. The environment is never read.
+ * Returns 0, ENOMEM, EINVAL (a null required pointer, rx->tcp_win missing, misaligned tx_conns / ack_conns, a call out of turn
+ * or with another n / nconns than the dk_tcp_rx_process call before it: nothing is written). */
+int dk_tcp_ack_process(dk_tcp_ctx* ctx, const dk_rx_results* rx, uint32_t n, const uint8_t* action,
+                       const dk_tcp_conn* rx_conns, dk_tcp_tx_conn* tx_conns, dk_tcp_ack_conn* ack_conns,
+                       uint32_t nconns, const dk_tcp_unacked* q, uint32_t nq, uint64_t now_ns,
+                       const dk_tcp_ack_out* out, void* stream);
 
 #ifdef __cplusplus
 }
