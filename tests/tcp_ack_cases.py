@@ -42,6 +42,12 @@ class Script:
     wscale: int = 0
     extra_flight: int = 0       # sequence space in flight that no queue entry covers (a dry queue)
     bad: dict = field(default_factory=dict)  # "tx__state" etc.: a field overwritten in the tables
+    tx_times: list | None = None  # the queue entries' transmit times, given (qn = their number; no marker's)
+    rto: tuple | None = None    # the RTO state the call starts from: (srtt, rttvar, rto, received_sample)
+
+    def __post_init__(self):
+        if self.tx_times is not None:
+            self.qn = len(self.tx_times)
 
 
 def offsets(rng, s: Script, lens: np.ndarray) -> np.ndarray:
@@ -70,8 +76,9 @@ def offsets(rng, s: Script, lens: np.ndarray) -> np.ndarray:
     return o.astype(np.int64)
 
 
-def build(scripts: list[Script], seed: int = 1, udp_every: int = 9):
-    """-> dict: flows, blob/off/lens (the frames), rx/tx/ak tables, pool arrays, now."""
+def build(scripts: list[Script], seed: int = 1, udp_every: int = 9, now: int = NOW):
+    """-> dict: flows, blob/off/lens (the frames), rx/tx/ak tables, pool arrays, now (the call's clock, below NONE)."""
+    assert 3 * 10**9 <= now < NONE
     rng = np.random.default_rng(seed)
     nc = len(scripts)
     flows = np.concatenate([synth.make_flows(nc, seed=seed), synth.make_flows(2, kind="udp")])
@@ -85,13 +92,16 @@ def build(scripts: list[Script], seed: int = 1, udp_every: int = 9):
         una = int(rng.integers(0, 1 << 32)) if s.una is None else s.una & M32
         rn = int(rng.integers(0, 1 << 32)) if s.rn is None else s.rn & M32
         lens = rng.integers(1, 1461, s.qn)
-        txt = (NOW - rng.integers(10**5, 3 * 10**9, s.qn)).astype(np.uint64)
+        txt = np.uint64(now) - rng.integers(10**5, 3 * 10**9, s.qn).astype(np.uint64)
         r = rng.random(s.qn)
         txt[r < 0.3] = NONE  # retransmitted entries, interleaved
-        txt[(r >= 0.3) & (r < 0.4)] = NOW + 12345  # a transmit time ahead of now: the difference saturates at 0
+        # a transmit time ahead of now: the difference saturates at 0
+        txt[(r >= 0.3) & (r < 0.4)] = min(now + 12345, NONE - 1)
+        if s.tx_times is not None:
+            txt = np.array(s.tx_times, np.uint64)
         qlens, qtx = list(lens), list(txt)
         if s.marker:
-            qlens.append(0), qtx.append(NOW - 777)
+            qlens.append(0), qtx.append(now - 777)
         # some slack in front of every queue, so q_first is not a multiple of anything
         pad = int(rng.integers(0, 3))
         pool["off"] += [0] * pad + list(rng.integers(0, 1 << 20, len(qlens)))
@@ -104,6 +114,8 @@ def build(scripts: list[Script], seed: int = 1, udp_every: int = 9):
         rx["receive_next"][c] = rx["reader_next"][c] = rn
         rx["send_next"][c] = nxt
         ak["wl1"][c], ak["wl2"][c], ak["snd_wscale"][c] = (rn + s.wl1_off) & M32, (una + s.wl2_off) & M32, s.wscale
+        if s.rto is not None:
+            ak["srtt"][c], ak["rttvar"][c], ak["rto"][c], ak["received_sample"][c] = s.rto
         # the segments
         o = offsets(rng, s, lens)
         if s.stream == "reordered":  # swap neighbours' acks; the seqs below get their own disorder from "stored"
@@ -174,7 +186,90 @@ def build(scripts: list[Script], seed: int = 1, udp_every: int = 9):
     pool = {"off": np.array(pool["off"], np.uint32), "len": np.array(pool["len"], np.uint32),
             "tx_time": np.array(pool["tx_time"], np.uint64)}
     return {"flows": flows, "blob": blob, "off": off, "lens": lens, "rx": rx, "tx": tx, "ak": ak, "pool": pool,
-            "now": NOW, "n": n, "nconns": nrows}
+            "now": now, "n": n, "nconns": nrows}
+
+
+# RTT samples d = now - tx_time in nanoseconds, in queue order: around one second (where Duration::as_secs_f64 splits
+# whole seconds from nanoseconds), around 2^32 ns (4.29 s: what 32-bit arithmetic on d loses), around the RTO's upper
+# clamp of 60 s, above 2^53 (the whole seconds no longer fit f64 once multiplied out), at 2^63 (the sign bit of an
+# int64 difference) and the largest there is.
+EXTREME_D = (0, 1, 999999999, 10**9, 10**9 + 1, 2**32 - 1, 2**32, 2**32 + 1, 599 * 10**8, 60 * 10**9, 100 * 10**9,
+             2**53 + 1, 2**63, 2**64 - 2)
+EXTREME_NOWS = (2**64 - 2, 2**63)
+BACKED_OFF = (0.2, 0.01, 8.0, 1)  # an RTO state after samples and one host back-off (rto is not srtt + 4 rttvar)
+
+
+def extreme_times(now: int, ds=EXTREME_D, ahead: bool = True) -> list:
+    """Transmit times that give the samples `ds` (those that fit below `now`) in order, a NONE entry after every
+    third and, where `now` leaves room above it, entries with tx_time > now (no sample of theirs is negative: it
+    saturates at 0). At now = 2^64 - 2 the only value above now is NONE itself."""
+    out = []
+    for k, d in enumerate(d for d in ds if d <= now):
+        out.append(now - d)
+        if k % 3 == 2:
+            out.append(NONE)
+        if ahead and k % 4 == 1 and now + 1 < NONE:
+            out.append((now + 1, NONE - 1)[k // 4 % 2])
+    return out
+
+
+def extremes(now: int):
+    """One batch at clock `now`: the RTT / RTO extremes, one connection per line. Every ACK stream is all_nxt or rising
+    without drops between, so every entry is popped and the samples taken are exactly the entries with a time."""
+    cyc = lambda k: [now - EXTREME_D[(7 * i) % len(EXTREME_D)] for i in range(k)  # noqa: E731
+                     if EXTREME_D[(7 * i) % len(EXTREME_D)] <= now]
+    scripts = [
+        Script(m=9, mixed=False, tx_times=extreme_times(now)),
+        # the same list from entry 65 on and 200 more behind: the wave form folds 64 entries a step
+        Script(m=12, mixed=False, marker=True, tx_times=cyc(130)[:65] + extreme_times(now) + cyc(400)[:200]),
+        Script(m=5, mixed=False, stream="all_nxt", tx_times=[now - d for d in (0, 1, 500, 1000, 999, 1000, 7, 1000)]),
+        Script(m=5, mixed=False, tx_times=[now - d for d in (60 * 10**9, 100 * 10**9, 2**53 + 1, 2**63, 60 * 10**9)]),
+        Script(m=4, mixed=False, stream="all_nxt", tx_times=[NONE, now - (2**32 - 1), NONE]),
+        Script(m=6, mixed=False, rto=BACKED_OFF, tx_times=[NONE] * 5),
+        Script(m=6, mixed=False, rto=BACKED_OFF, tx_times=[NONE, now - 3 * 10**8, NONE]),
+        # srtt the smallest subnormal: 0.875 * srtt + 0 rounds back to it, a flush to zero would not
+        Script(m=6, mixed=False, rto=(5e-324, 1e300, 1.0, 1), tx_times=[now] * 3),
+        Script(m=6, mixed=False, rto=(5e-324, 1e300, 1.0, 1), tx_times=[now - d for d in (0, 0, 1, 10**9, 0)]),
+    ]
+    case = build(scripts, seed=123, now=now)
+    case["scripts"] = scripts
+    return case
+
+
+def check_extremes(case: dict, exp: dict) -> None:
+    """What the lines of extremes() are there for, asserted on a result (the reference's, which the device's equals
+    bit for bit)."""
+    a, now = exp["ack_conns"], case["now"]
+    nc = len(case["scripts"])
+    assert (exp["status"][:nc] == 0).all() and (a["q_count"][:nc] == 0).all(), exp["status"]
+    for c, s in enumerate(case["scripts"]):  # the samples taken are known: every entry with a time, and the marker
+        assert exp["samples"][c] == sum(t != NONE for t in s.tx_times) + int(s.marker), (c, exp["samples"][c])
+    assert a["rto"][2] == 0.1 and 4.0 * a["rttvar"][2] < 0.001
+    assert a["rto"][3] == 60.0 and a["srtt"][3] > 60.0
+    assert exp["samples"][4] == 1 and a["received_sample"][4] == 1
+    assert a["srtt"][4] == 4.0 + 294967295 / 1e9 and a["rttvar"][4] == a["srtt"][4] / 2.0
+    before = case["ak"]
+    assert exp["new_acks"][5] > 0 and exp["samples"][5] == 0 and a["rto"][5] == 8.0
+    for k in ("srtt", "rttvar", "rto"):
+        assert a[k][5].tobytes() == before[k][5].tobytes(), k
+    assert a["srtt"][6] == 0.875 * 0.2 + 0.125 * 0.3 and a["rttvar"][6] == 0.75 * 0.01 + 0.25 * abs(0.2 - 0.3)
+    assert a["rto"][6] == a["srtt"][6] + 4.0 * a["rttvar"][6] != 8.0
+    assert a["srtt"][7] == 5e-324 and a["rttvar"][7] == 0.75 * (0.75 * (0.75 * 1e300)) and a["rto"][7] == 60.0
+    assert a["rto"][8] == 60.0 and 0.1 < a["srtt"][8] < 0.2
+    if now == 2**64 - 2:  # the last sample is 18,446,744,073 s + 0.709551614: an eighth of it is in srtt
+        assert a["srtt"][0] > (2**64 - 2) // 10**9 / 8 and a["rto"][0] == 60.0
+
+
+def host_actions(case: dict) -> dict:
+    """The batch through the CPU restatement of the receive chain: what dk_rx_process and dk_tcp_rx_process hand to
+    the ACK pass (flow_id, tcp_seq, tcp_ack, tcp_win, action)."""
+    from oracle import oracle as O
+
+    peer = O.OraclePeer(synth.ipv4(synth.BOB_IPV4))
+    peer.set_flows(case["flows"])
+    rx = peer.process(case["blob"], case["off"], case["lens"])
+    rx["action"] = O.tcp_process(case["rx"].copy(), rx)["action"]
+    return rx
 
 
 def shapes(nconns: int, big: bool = True) -> list[Script]:

@@ -220,6 +220,22 @@ def test_queues(form):
 
 
 @functools.lru_cache(maxsize=None)
+def case_extremes(now: int):
+    return C.extremes(now)
+
+
+@pytest.mark.parametrize("form", FORMS)
+@pytest.mark.parametrize("now", C.EXTREME_NOWS)
+def test_rtt_and_rto_extremes(now, form):
+    """RTT samples from 0 to 2^64 - 2 ns at a clock of 2^64 - 2 (and at 2^63, where transmit times above the clock
+    exist), RTO states on both clamps, carried and backed off by the host, srtt subnormal: tcp_ack_cases.extremes.
+    tests/test_tcp_ack_model.py shows that a sample cut to 32 bits or taken as an int64 gives another srtt here."""
+    case = case_extremes(now)
+    exp = run(case, form)
+    C.check_extremes(case, exp)
+
+
+@functools.lru_cache(maxsize=None)
 def case_fallbacks():
     """Connections the wave form hands to its one lane: segments 2^30 behind wl1 or 3 * 2^29 ahead of it, wl2 2^31 behind
     SND.NXT, a marker in the middle of the queue swallowing a remainder, bytes acknowledged behind the marker."""

@@ -9,6 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import tcp_ack_cases as C
 import tcp_ack_reference as R
 from demikernel_amd import _native as N
 from demikernel_amd.tcp import conn_table
@@ -55,6 +56,48 @@ def test_rto_answers_by_hand():
     r = R.Rto()
     r.add_sample_ns(2 * S + 250000000)  # as_secs_f64: whole seconds + nanos / 1e9
     assert r.srtt == 2.0 + 250000000 / 1e9 == 2.25
+
+
+def test_rtt_beyond_32_bits_by_hand():
+    r = R.Rto()
+    r.add_sample_ns(2**32 + 1)  # 4,294,967,297 ns: 4 s + 294,967,297 ns
+    assert r.srtt == 4.0 + 294967297 / 1e9 == 4.294967297 and r.rto == 4.294967297 + 4.0 * (4.294967297 / 2.0)
+    r = R.Rto()
+    r.add_sample_ns(2**53 + 1)  # 9,007,199,254,740,993 ns: not an f64; whole seconds and nanoseconds apart are
+    assert r.srtt == 9007199.0 + 254740993 / 1e9 == 9007199.254740993 and r.rto == 60.0
+    r = R.Rto()
+    r.add_sample_ns(2**64 - 2)
+    assert r.srtt == 18446744073.0 + 709551614 / 1e9
+
+
+def extremes_with(change, now):
+    """The reference over tcp_ack_cases.extremes(now) with every sample d replaced by change(d)."""
+    case = C.extremes(now)
+    h = C.host_actions(case)
+    plain = R.Rto.add_sample_ns
+    try:
+        if change is not None:
+            R.Rto.add_sample_ns = lambda self, d: plain(self, change(d))
+        return case, R.ack_process(h["flow_id"], h["action"], h["tcp_seq"], h["tcp_ack"], h["tcp_win"], case["rx"],
+                                   case["tx"], case["ak"], case["pool"], now)
+    finally:
+        R.Rto.add_sample_ns = plain
+
+
+@pytest.mark.parametrize("now", C.EXTREME_NOWS)
+def test_extremes_scenario_and_its_guards(now):
+    """The RTT / RTO extremes batch of the GPU tests does what it was built for, and tells the two wrong kernels it is
+    there for from a right one: d cut to 32 bits, and now - tx taken as an int64 (negative from 2^63: saturated)."""
+    case, exp = extremes_with(None, now)
+    C.check_extremes(case, exp)
+    _, masked = extremes_with(lambda d: d & 0xFFFFFFFF, now)
+    _, signed = extremes_with(lambda d: d if d < 2**63 else 0, now)
+    for c in (0, 1, 3):
+        assert masked["ack_conns"]["srtt"][c] != exp["ack_conns"]["srtt"][c], c
+        assert signed["ack_conns"]["srtt"][c] != exp["ack_conns"]["srtt"][c], c
+    # a transmit time above now gives the sample 0, not a huge one
+    if now + 1 < R.NONE:
+        assert any(t != R.NONE and t > now for t in case["scripts"][0].tx_times)
 
 
 def test_ack_splits_an_entry_then_pops_it_without_a_sample():
