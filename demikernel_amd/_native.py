@@ -236,6 +236,26 @@ TCP_TX_FUNCTIONS = [
                                   c_uint32, POINTER(DkTcpTxResults), c_void_p]),
 ]
 
+# include/dk_tcp.h, retransmission (dk_tcp_retransmit)
+DK_TCP_RTX_NONE, DK_TCP_RTX_TIMEOUT, DK_TCP_RTX_FAST = range(3)
+TCP_RTX_STATUSES = ["NOT_FIRED", "SENT", "IDLE", "E_FIRE", "E_STATE", "E_QUEUE", "E_RANGE", "E_SLOT", "E_LINK",
+                    "E_WINDOW", "NO_ROOM"]
+(DK_TCP_RTX_NOT_FIRED, DK_TCP_RTX_SENT, DK_TCP_RTX_IDLE, DK_TCP_RTX_E_FIRE, DK_TCP_RTX_E_STATE, DK_TCP_RTX_E_QUEUE,
+ DK_TCP_RTX_E_RANGE, DK_TCP_RTX_E_SLOT, DK_TCP_RTX_E_LINK, DK_TCP_RTX_E_WINDOW, DK_TCP_RTX_NO_ROOM) = range(11)
+DK_TCP_RTX_NO_FRAME = 0xFFFFFFFF
+TCP_RTX_RESULT_FIELDS = ["off_out", "len_out", "frame_conn", "status", "frame", "n_frames"]
+
+
+class DkTcpRtxResults(ctypes.Structure):
+    _fields_ = [(name, c_void_p) for name in TCP_RTX_RESULT_FIELDS]
+
+
+TCP_RTX_FUNCTIONS = [
+    ("dk_tcp_retransmit", c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p,
+                                  POINTER(DkTcpUnacked), c_uint32, c_uint64, c_void_p, c_uint32, c_void_p, c_uint64,
+                                  POINTER(DkTcpTxLayout), c_uint32, c_uint32, POINTER(DkTcpRtxResults), c_void_p]),
+]
+
 # include/dk_diag.h (diagnostics, not the receive ABI)
 # include/dk_demi.h: delivered frames as demi_sgarray_t (host-side, no GPU work)
 class DemiSgaseg(ctypes.Structure):
@@ -294,7 +314,8 @@ DK_TCP_WALKS = {"lane": 0, "wave": 1, "relay": 2, "scan": 3}
 DK_TCP_SORTS = {"counting": 0, "radix": 1}
 DK_TCP_ACK_FORMS = {"lane": 0, "wave": 1, "chip": 2}
 
-ALL_FUNCTIONS = (FUNCTIONS + RING_FUNCTIONS + TCP_FUNCTIONS + TCP_ACK_FUNCTIONS + TCP_TX_FUNCTIONS + DIAG_FUNCTIONS +
+ALL_FUNCTIONS = (FUNCTIONS + RING_FUNCTIONS + TCP_FUNCTIONS + TCP_ACK_FUNCTIONS + TCP_TX_FUNCTIONS + TCP_RTX_FUNCTIONS +
+                 DIAG_FUNCTIONS +
                  DEMI_FUNCTIONS + COMM_FUNCTIONS)
 
 _lib = None

@@ -233,6 +233,23 @@ DK_HD bool tcp_tx_fits(uint64_t total, uint32_t max_frames, uint32_t stride, uin
     return total <= max_frames && total * stride <= out_bytes;
 }
 
+// Retransmission (dk_tcp_retransmit, dk_tcp.h): the emit kernel's view of what rtx_plan (tcp_tx_kernels.hip) left.
+struct TcpRtxEmitParams {
+    const uint8_t* src;
+    uint8_t* out;
+    uint64_t out_bytes;
+    const dk_tcp_tx_conn* tx;
+    const dk_tx_link* links;
+    const uint64_t* first;  // [nconns] exclusive scan of the connections' emit flags: a connection's frame index
+    const uint64_t* total;  // the frames the call needs
+    const uint32_t* rec;    // [nconns][4], 16-byte aligned: the front's off, len | window << 16, seq, ack number
+    uint32_t nconns;
+    uint32_t stride, lead, max_frames, flags;
+    uint32_t* off_out;
+    uint16_t* len_out;
+    uint32_t* frame_conn;  // nullable
+};
+
 // TcpHeader::compute_size (tcp/header.rs:408-421) of an option list: 20 + the entries' sizes (TcpOptions2::compute_size
 // :43-54; a SACK entry's blocks must lie inside sack[]) + one EndOfOptionsList byte when the list is not empty, rounded
 // up to 4. 0 when the list cannot be serialized (more than 5 entries, unknown kind, SACK with 0 or > 4 blocks, more
@@ -282,3 +299,4 @@ int dk_tx_serialize_resident_blocks();  // occupancy of dk_tx_serialize_kernel p
 int dk_launch_tx_serialize(const dk::TxSerParams& p, uint32_t grid, void* stream);
 int dk_tcp_tx_emit_resident_blocks();  // occupancy of dk_tcp_tx_emit_kernel per CU (0 on error)
 int dk_launch_tcp_tx_emit(const dk::TcpTxEmitParams& p, uint32_t grid, void* stream);
+int dk_launch_tcp_rtx_emit(const dk::TcpRtxEmitParams& p, uint32_t grid, void* stream);

@@ -2718,6 +2718,101 @@ __global__ __launch_bounds__(kBlock) void dk_tcp_tx_emit_kernel(TcpTxEmitParams 
     }
 }
 
+// Retransmission, emit pass (dk_tcp_retransmit, dk_tcp.h): the kernel above with a connection's front queue entry in
+// place of a pushed buffer's piece. It is frame-major: rtx_plan (tcp_tx_kernels.hip) left, per connection, a record of
+// the entry and the header fields, and the exclusive scan of the emit flags numbers the frames, so frame f belongs to
+// the largest c with first[c] <= f (the connection that emits is the last one holding its scan value). A burst of 200
+// in a table of 100k connections costs 200 searches and 200 frames' copies; no wave walks the table. The entry goes out
+// whole, whatever the connection's mss is now; PSH or FIN follows from its length.
+__global__ __launch_bounds__(kBlock) void dk_tcp_rtx_emit_kernel(TcpRtxEmitParams P) {
+    const uint64_t total = *P.total;
+    if (!tcp_tx_fits(total, P.max_frames, P.stride, P.out_bytes)) return;  // all or nothing, as rtx_commit tests it
+    const uint32_t n = (uint32_t)total;
+    const uint32_t lane = lane_id(), wv = threadIdx.x >> 6;
+    const uint32_t nw = gridDim.x * kWaves, gw = blockIdx.x * kWaves + wv;
+    // A wave takes `per` frames a round: 64 when every wave of the grid has that many, else the power of two (4 at the
+    // least: one per quarter) that spreads the call's frames over the grid, so that a burst of a few hundred frames is
+    // not copied by a handful of waves, four frames at a time, while the rest of the chip idles.
+    uint32_t per = 64 / kTxSub;
+    while (per < 64 && (uint64_t)per * nw < n) per <<= 1;
+    const uint32_t nchunks = n / per + (n % per != 0);
+    for (uint32_t ch = gw; ch < nchunks; ch += nw) {
+        const uint32_t f0 = ch * per, f = f0 + lane;
+        const bool live = lane < per && f < n;
+        uint32_t plen = 0, seq = 0, ack = 0, win = 0, b13 = 0x10u, conn = 0, so = 0;
+        if (live) {
+            uint32_t lo = 0, hi = P.nconns;  // the last connection whose frame index is <= f
+            while (hi - lo > 1) {
+                const uint32_t mid = lo + (hi - lo) / 2;
+                if (P.first[mid] <= f) lo = mid;
+                else hi = mid;
+            }
+            conn = lo;
+            const uint4 r = reinterpret_cast<const uint4*>(P.rec)[conn];
+            so = r.x;
+            plen = r.y & 0xFFFFu;
+            win = r.y >> 16;
+            seq = r.z;
+            ack = r.w;
+            b13 = 0x10u | (plen ? 0x08u : 0x01u);  // retransmit(): PSH on data, FIN for the marker (sender.rs:396-401)
+        }
+        const uint32_t foff = (uint32_t)((uint64_t)f * P.stride + P.lead);
+        uint32_t src = 0, dst = 0, ports = 0, ipw = 0;
+        uint3 Lk = make_uint3(0, 0, 0);
+        if (live) {
+            __builtin_nontemporal_store(foff, gptr(P.off_out) + f);
+            __builtin_nontemporal_store((uint16_t)(54u + plen), gptr(P.len_out) + f);
+            if (P.frame_conn) __builtin_nontemporal_store(conn, gptr(P.frame_conn) + f);
+            const dk_tcp_tx_conn& T = P.tx[conn];
+            src = T.local_ip, dst = T.remote_ip, ports = T.ports, ipw = T.ip_word;
+            const uint32_t* lw = reinterpret_cast<const uint32_t*>(P.links + T.link);
+            Lk = make_uint3(lw[0], lw[1], lw[2]);
+        }
+        const uint32_t cnt = min(per, n - f0);
+        const uint32_t sub = lane & (kTxSub - 1), q = lane / kTxSub;
+        for (uint32_t t = 0; t < cnt; t += 64 / kTxSub) {  // quarter q copies frame t + q
+            const uint32_t fr = t + q;
+            const uint32_t sf = (uint32_t)__shfl((int)so, (int)fr);
+            const uint32_t lf = (uint32_t)__shfl((int)plen, (int)fr);  // every lane shuffles, as above
+            const uint32_t L = fr < cnt ? lf : 0u;
+            uint8_t* pay = P.out + ((uint64_t)(f0 + fr) * P.stride + P.lead + 54u);
+            const uint32_t s = tcp_tx_copy_sum(P.src + sf, pay, L, sub);
+            const uint32_t le = (uint32_t)__shfl((int)s, (int)(((lane - t) & (64 / kTxSub - 1)) * kTxSub));
+            if (!(live && lane >= t && lane < t + 64 / kTxSub)) continue;
+            // the header arithmetic of dk_tcp_tx_emit_kernel
+            const uint32_t tot = 40u + plen, seg = 20u + plen;
+            const uint32_t ident = ipw & 0xFFFFu, ttl = (ipw >> 16) & 0xFFu, tos = ipw >> 24;
+            const uint32_t ipsum = (0x4500u | tos) + tot + ident + 0x4000u + ((ttl << 8) | 6u) + ip_be_sum(src) + ip_be_sum(dst);
+            const uint32_t ipc = csum_from_residue(mod_ffff(ipsum));
+            const uint32_t sport = ports & 0xFFFFu, dport = ports >> 16;
+            const uint32_t b12 = 5u << 4;
+            uint32_t c = 0;
+            if (!(P.flags & DK_TX_OFFLOAD_TCP)) {
+                const uint32_t be = ip_be_sum(src) + ip_be_sum(dst) + 6u + seg + sport + dport + be16_sum(seq) +
+                                    be16_sum(ack) + ((b12 << 8) | b13) + win;
+                c = csum_from_residue(mod_ffff(be_residue(le) + be));
+            }
+            uint32_t d[14];
+            d[0] = Lk.x;
+            d[1] = Lk.y;
+            d[2] = Lk.z;
+            d[3] = 0x0008u | 0x45u << 16 | tos << 24;
+            d[4] = bswap16(tot) | bswap16(ident) << 16;
+            d[5] = 0x0040u | ttl << 16 | 6u << 24;
+            d[6] = bswap16(ipc) | (src & 0xFFFFu) << 16;
+            d[7] = (src >> 16) | (dst & 0xFFFFu) << 16;
+            d[8] = (dst >> 16) | bswap16(sport) << 16;
+            const uint32_t sq = __builtin_bswap32(seq), ak = __builtin_bswap32(ack);
+            d[9] = bswap16(dport) | sq << 16;
+            d[10] = (sq >> 16) | ak << 16;
+            d[11] = (ak >> 16) | b12 << 16 | b13 << 24;
+            d[12] = bswap16(win) | bswap16(c) << 16;
+            d[13] = 0;
+            tx_store_header(P.out + foff, d, true);
+        }
+    }
+}
+
 }  // namespace
 }  // namespace dk
 
@@ -2847,5 +2942,11 @@ int dk_tcp_tx_emit_resident_blocks() {
 int dk_launch_tcp_tx_emit(const dk::TcpTxEmitParams& p, uint32_t grid, void* stream) {
     if (p.nbufs == 0 || grid == 0) return 0;
     hipLaunchKernelGGL(dk::dk_tcp_tx_emit_kernel, dim3(grid), dim3(dk::kBlock), 0, (hipStream_t)stream, p);
+    return hipGetLastError() == hipSuccess ? 0 : 5;
+}
+
+int dk_launch_tcp_rtx_emit(const dk::TcpRtxEmitParams& p, uint32_t grid, void* stream) {
+    if (p.nconns == 0 || grid == 0) return 0;
+    hipLaunchKernelGGL(dk::dk_tcp_rtx_emit_kernel, dim3(grid), dim3(dk::kBlock), 0, (hipStream_t)stream, p);
     return hipGetLastError() == hipSuccess ? 0 : 5;
 }

@@ -1,6 +1,6 @@
-// tcp_tx_kernels.hip — dk_tcp_tx_segment (dk_tcp.h): the plan and commit kernels and the host entry points. The emit
-// kernel (the payload copy, the checksums and the headers) is dk_tcp_tx_emit_kernel in rx_kernels.hip, next to the
-// dk_tx_serialize code it shares its header arithmetic with.
+// tcp_tx_kernels.hip — dk_tcp_tx_segment and dk_tcp_retransmit (dk_tcp.h): the plan and commit kernels and the host
+// entry points. The emit kernels (the payload copy, the checksums and the headers) are dk_tcp_tx_emit_kernel and
+// dk_tcp_rtx_emit_kernel in rx_kernels.hip, next to the dk_tx_serialize code they share their header arithmetic with.
 //
 // Sender::send_segment (tcp/established/sender.rs:124-208) cuts one segment at a time, each as large as
 // min(send window - in flight, MSS, cwnd - in flight) allows. With no ACK arriving inside a call the windows are fixed,
@@ -235,6 +235,91 @@ __global__ __launch_bounds__(kBlock) void commit_kernel(Plan P) {
     }
 }
 
+// dk_tcp_retransmit (dk_tcp.h): one lane per connection plans (the checks in the header's order, emit 0/1, the front
+// entry and the header fields as a record), the scan above numbers the frames, dk_tcp_rtx_emit_kernel (rx_kernels.hip)
+// builds them, and one lane per connection commits behind the same capacity test.
+struct RtxPlan {
+    uint64_t src_bytes, out_bytes, now_ns;
+    const uint8_t* fire;
+    const dk_tcp_tx_conn* tx;
+    dk_tcp_ack_conn* ak;
+    const dk_tcp_conn* rx;
+    dk_tcp_unacked q;
+    uint32_t nconns, nq, nlinks;
+    uint32_t stride, lead, max_frames;
+    uint64_t* emit;  // [nconns] emit flags, then their exclusive scan
+    uint64_t* tot;   // the frames the call needs
+    uint4* rec;      // [nconns] the front's off, len | window << 16, seq, ack number (the emit kernel's)
+    dk_tcp_rtx_results res;
+};
+
+__global__ __launch_bounds__(kBlock) void rtx_plan(RtxPlan P) {
+    const uint32_t c = blockIdx.x * kBlock + threadIdx.x;
+    if (c >= P.nconns) return;
+    const uint32_t fire = P.fire[c];
+    uint32_t st = DK_TCP_RTX_NOT_FIRED;
+    uint4 rec = make_uint4(0, 0, 0, 0);
+    if (fire > DK_TCP_RTX_FAST) {
+        st = DK_TCP_RTX_E_FIRE;
+    } else if (fire) {
+        const dk_tcp_tx_conn T = P.tx[c];
+        const dk_tcp_ack_conn& A = P.ak[c];
+        const uint32_t qf = A.q_first, qc = A.q_count;
+        uint64_t w = T.rcv_wnd_hdr;
+        uint32_t ack = T.rcv_nxt;
+        if (P.rx) {  // as plan_kernel: RCV.NXT and hdr_window_size
+            const dk_tcp_conn& R = P.rx[c];
+            const uint32_t rn = R.receive_next;
+            ack = rn;
+            const uint32_t ws = T.rcv_wscale;
+            w = ws > 31 ? 0u : (uint32_t)(R.buffer_size - (rn - R.reader_next)) >> ws;
+        }
+        if (T.state != DK_TCP_ESTABLISHED) st = DK_TCP_RTX_E_STATE;
+        else if ((uint64_t)qf + qc > P.nq) st = DK_TCP_RTX_E_QUEUE;
+        else if (T.link >= P.nlinks) st = DK_TCP_RTX_E_LINK;
+        else if (w > 0xFFFFu) st = DK_TCP_RTX_E_WINDOW;
+        else if (qc == 0 || (fire == DK_TCP_RTX_TIMEOUT && !A.rtx_armed)) st = DK_TCP_RTX_IDLE;
+        else {
+            const uint32_t off = P.q.off[qf], len = P.q.len[qf];
+            if ((uint64_t)off + len > P.src_bytes) st = DK_TCP_RTX_E_RANGE;
+            else if (len > kMaxMss || (uint64_t)P.lead + 54u + len > P.stride) st = DK_TCP_RTX_E_SLOT;
+            else {
+                st = DK_TCP_RTX_SENT;
+                rec = make_uint4(off, len | (uint32_t)w << 16, T.snd_una, ack);
+            }
+        }
+    }
+    P.emit[c] = st == DK_TCP_RTX_SENT;
+    P.rec[c] = rec;
+    P.res.status[c] = st;  // SENT stands unless rtx_commit finds no room
+}
+
+__global__ __launch_bounds__(kBlock) void rtx_commit(RtxPlan P) {
+    const uint32_t c = blockIdx.x * kBlock + threadIdx.x;
+    if (c >= P.nconns) return;
+    const uint64_t total = P.tot[0];
+    const bool fits = dk::tcp_tx_fits(total, P.max_frames, P.stride, P.out_bytes);
+    if (c == 0) *P.res.n_frames = (uint32_t)total;  // at most nconns
+    const uint64_t first = P.emit[c];
+    const bool emits = (c + 1 < P.nconns ? P.emit[c + 1] : total) != first;
+    P.res.frame[c] = emits && fits ? (uint32_t)first : 0xFFFFFFFFu;
+    if (!emits) return;
+    if (!fits) {
+        P.res.status[c] = DK_TCP_RTX_NO_ROOM;
+        return;
+    }
+    dk_tcp_ack_conn& A = P.ak[c];
+    P.q.tx_time[A.q_first] = DK_TCP_TX_TIME_NONE;  // Karn: no sample from a retransmitted entry
+    if (P.fire[c] == DK_TCP_RTX_TIMEOUT) {
+        double r = A.rto * 2.0;  // RtoCalculator::back_off -> update_rto's clamp
+        if (r < 0.1) r = 0.1;
+        if (r > 60.0) r = 60.0;
+        A.rto = r;
+        A.rtx_base_ns = P.now_ns;
+        A.rtx_armed = 1;
+    }
+}
+
 struct DeviceGuard {
     int prev = -1;
     explicit DeviceGuard(int dev) {
@@ -286,6 +371,10 @@ struct dk_tcp_tx_ctx {
     uint4* rec = nullptr;
     uint2* cm = nullptr;
     size_t rec_cap = 0, cm_cap = 0;
+    // dk_tcp_retransmit's: the emit flags / their scan and the records per connection (tot[3] is its total)
+    uint64_t* rtx_emit = nullptr;
+    uint4* rtx_rec = nullptr;
+    size_t rtx_emit_cap = 0, rtx_rec_cap = 0;
 };
 
 extern "C" {
@@ -326,7 +415,7 @@ void dk_tcp_tx_ctx_destroy(dk_tcp_tx_ctx* t) {
     dk_tcp_tx::DeviceGuard g(t->device);
     if (t->used) (void)hipEventSynchronize(t->last);
     for (void* p : {(void*)t->seqsp, (void*)t->flags, (void*)t->frames, (void*)t->bsum, (void*)t->tot, (void*)t->head,
-                    (void*)t->tail, (void*)t->rec, (void*)t->cm})
+                    (void*)t->tail, (void*)t->rec, (void*)t->cm, (void*)t->rtx_emit, (void*)t->rtx_rec})
         if (p) (void)hipFree(p);
     (void)hipEventDestroy(t->last);
     delete t;
@@ -386,6 +475,56 @@ int dk_tcp_tx_segment(dk_tcp_tx_ctx* t, const uint8_t* src, uint64_t src_bytes, 
         if (cap > 0) grid = std::min(grid, (uint32_t)cap);
         if (max_frames && (rc = dk_launch_tcp_tx_emit(E, grid, s))) return EIO;
         hipLaunchKernelGGL(commit_kernel, per_buf, dim3(kBlock), 0, s, P);
+        if (hipGetLastError() != hipSuccess) return EIO;
+    }
+    if (hipEventRecord(t->last, s) != hipSuccess) return EIO;
+    t->last_stream = s;
+    t->used = true;
+    return 0;
+}
+
+int dk_tcp_retransmit(dk_tcp_tx_ctx* t, const uint8_t* src, uint64_t src_bytes, const uint8_t* fire,
+                      const dk_tcp_tx_conn* tx_conns, dk_tcp_ack_conn* ack_conns, uint32_t nconns,
+                      const dk_tcp_conn* rx_conns, const dk_tcp_unacked* q, uint32_t nq, uint64_t now_ns,
+                      const dk_tx_link* links, uint32_t nlinks, uint8_t* out, uint64_t out_bytes,
+                      const dk_tcp_tx_layout* layout, uint32_t max_frames, uint32_t flags,
+                      const dk_tcp_rtx_results* res, void* stream) {
+    using namespace dk_tcp_tx;
+    if (!t || !layout || !res || !res->n_frames || !q || !links || nlinks == 0) return EINVAL;
+    if (src_bytes > DK_RX_MAX_BLOB || out_bytes > DK_RX_MAX_BLOB) return EINVAL;
+    if ((reinterpret_cast<uintptr_t>(tx_conns) | reinterpret_cast<uintptr_t>(ack_conns) |
+         reinterpret_cast<uintptr_t>(rx_conns)) & 15)
+        return EINVAL;
+    if (nconns && (!fire || !tx_conns || !ack_conns || !res->status || !res->frame || (src_bytes && !src) ||
+                   (nq && (!q->off || !q->len || !q->tx_time))))
+        return EINVAL;
+    if (nconns && max_frames && (!out || !res->off_out || !res->len_out)) return EINVAL;
+    DeviceGuard g(t->device);
+    const hipStream_t s = (hipStream_t)stream;
+    if (t->used && t->last_stream != s && hipStreamWaitEvent(s, t->last, 0) != hipSuccess) return EIO;
+    if (nconns == 0) {
+        if (hipMemsetAsync(res->n_frames, 0, sizeof(uint32_t), s) != hipSuccess) return EIO;
+    } else {
+        const uint32_t nb = (nconns + kTile - 1) / kTile;
+        const bool grows = t->rtx_emit_cap < nconns || t->rtx_rec_cap < nconns || t->bsum_cap < nb;
+        if (t->used && grows && hipEventSynchronize(t->last) != hipSuccess) return EIO;  // in-flight work on the scratch
+        int rc = 0;
+        if ((rc = grow(t->rtx_emit, t->rtx_emit_cap, nconns)) || (rc = grow(t->rtx_rec, t->rtx_rec_cap, nconns)) ||
+            (rc = grow(t->bsum, t->bsum_cap, nb)))
+            return rc;
+        RtxPlan P{src_bytes, out_bytes, now_ns, fire, tx_conns, ack_conns, rx_conns, *q, nconns, nq, nlinks,
+                  layout->slot_stride, layout->frame_lead, max_frames, t->rtx_emit, t->tot + 3, t->rtx_rec, *res};
+        const dim3 per_conn((nconns + kBlock - 1) / kBlock);
+        hipLaunchKernelGGL(rtx_plan, per_conn, dim3(kBlock), 0, s, P);
+        if ((rc = scan(t->rtx_emit, nullptr, nconns, t->bsum, nb, t->tot + 3, nullptr, s))) return rc;
+        // emit reads the records, never the rows the commit writes, and runs first
+        dk::TcpRtxEmitParams E{src, out, out_bytes, tx_conns, links, t->rtx_emit, t->tot + 3,
+                               reinterpret_cast<const uint32_t*>(t->rtx_rec), nconns, layout->slot_stride,
+                               layout->frame_lead, max_frames, flags, res->off_out, res->len_out, res->frame_conn};
+        // sized from what the host knows: a frame per connection at most, and no more than the outputs have room for
+        const uint32_t grid = std::min<uint32_t>(std::min(max_frames, nconns) / 256 + 1, std::min(t->occ, 8u) * t->cus);
+        if (max_frames && dk_launch_tcp_rtx_emit(E, grid, s)) return EIO;
+        hipLaunchKernelGGL(rtx_commit, per_conn, dim3(kBlock), 0, s, P);
         if (hipGetLastError() != hipSuccess) return EIO;
     }
     if (hipEventRecord(t->last, s) != hipSuccess) return EIO;

@@ -17,10 +17,12 @@
  * pushes an empty buffer before the EOF buffer (ctrlblk.rs:693 + :1008).
  * The sender's reaction to the ACKs those segments carry (SND.UNA, the send window, the unacknowledged queue, the RTT
  * estimate and the retransmit deadline) is dk_tcp_ack_process and cutting pushed buffers into segments is
- * dk_tcp_tx_segment, both below.
- * Not modelled: the delayed-ACK timer and the ACKs segments trigger, congestion control (on_ack_received: the host
- * replays it from dk_tcp_ack_out), the retransmit timer's firing and retransmit() itself, states other than
- * ESTABLISHED (FIN-WAIT-1/2 etc.).
+ * dk_tcp_tx_segment, both below; resending the front of the unacknowledged queue (retransmit() and the timeout's
+ * back-off) is dk_tcp_retransmit, at the end.
+ * Not modelled: the delayed-ACK timer and the ACKs segments trigger, congestion control (on_ack_received,
+ * on_rto and on_fast_retransmit: the host replays them from dk_tcp_ack_out and from what it fires), deciding which
+ * retransmit timers have expired (the host compares rtx_base_ns + rto with its clock and names the connections in
+ * dk_tcp_retransmit's fire[]), states other than ESTABLISHED (FIN-WAIT-1/2 etc.).
  *
  * Conventions as dk_rx.h: 0 or a positive errno; device pointers; asynchronous on the caller's stream. A context holds
  * one set of scratch buffers: calls on one context are serialised — a call on another stream than the previous call
@@ -134,10 +136,10 @@ int dk_tcp_rx_process(dk_tcp_ctx* ctx, const dk_rx_results* rx, uint32_t n, dk_t
  * A sent FIN sets fin_sent; buffers behind a marker, or on a connection whose fin_sent is set, are not sent. The
  * payload is copied from the source blob into frame slots (a pushed buffer has no headroom between its pieces) and
  * summed while it is copied: each payload byte is read once and written once.
- * Not modelled (they stay with the host): retransmission and the timers' firing, cwnd updates (cwnd is an input, fixed
- * for the call: CUBIC's decrement of its limited-transmit increase in on_send and its idle restart in
- * on_cwnd_check_before_send are not applied between the frames of a call), the persist timer. The unacknowledged queue
- * and the RTT estimate are dk_tcp_ack_process's (below).
+ * Not modelled (they stay with the host): the timers' firing (retransmission itself is dk_tcp_retransmit, below), cwnd
+ * updates (cwnd is an input, fixed for the call: CUBIC's decrement of its limited-transmit increase in on_send and its
+ * idle restart in on_cwnd_check_before_send are not applied between the frames of a call), the persist timer. The
+ * unacknowledged queue and the RTT estimate are dk_tcp_ack_process's (below).
  * These entry points are additive: DK_RX_ABI_VERSION stays 4.
  * ------------------------------------------------------------------------------------------------------------- */
 /* Send side of one connection (Sender + what ControlBlock::tcp_header reads). Device memory, 16-byte aligned, updated
@@ -328,6 +330,83 @@ int dk_tcp_ack_process(dk_tcp_ctx* ctx, const dk_rx_results* rx, uint32_t n, con
                        const dk_tcp_conn* rx_conns, dk_tcp_tx_conn* tx_conns, dk_tcp_ack_conn* ack_conns,
                        uint32_t nconns, const dk_tcp_unacked* q, uint32_t nq, uint64_t now_ns,
                        const dk_tcp_ack_out* out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Retransmission: Sender::retransmit (sender.rs:375-403) and the timeout branch of background_retransmitter
+ * (sender.rs:347-364) with RtoCalculator::back_off (rto.rs:82-84), for every connection of a table at once. The
+ * unacknowledged queue holds only {off, len, tx_time} into the source blob, which lives in device memory: the frame
+ * is that payload again under fresh headers, copied and summed in one pass as dk_tcp_tx_segment does it.
+ * fire[0 .. nconns) is a device array the host fills: DK_TCP_RTX_TIMEOUT for a connection whose deadline
+ * rtx_base_ns + Duration(rto) has passed, DK_TCP_RTX_FAST for one its congestion control flagged (retransmit_now),
+ * 0 for the others. Deciding who fires stays with the host, as do congestion_control_on_rto / on_fast_retransmit and
+ * the Duration::from_secs_f64 conversion: after a TIMEOUT the host re-arms its timer at rtx_base_ns (= now_ns) +
+ * Duration(the connection's new rto).
+ * Per connection c with fire[c] != 0, in connection order, the first of these that applies gives its status:
+ *   the connection's own checks: E_FIRE, E_STATE, E_QUEUE, E_LINK, E_WINDOW (the header window as dk_tcp_tx_segment
+ *     computes it: from rx_conns[c] when given, else rcv_wnd_hdr);
+ *   IDLE: q_count == 0 (retransmit() returns at once), or TIMEOUT with rtx_armed == 0 (a None deadline cannot
+ *     time out);
+ *   the front entry's checks: E_RANGE, E_SLOT.
+ * Every status but SENT leaves everything of the connection untouched and builds no frame. One deviation: in the
+ * reference an armed timer over an empty queue would still back off and re-arm; that state is unreachable there
+ * (process_ack disarms on an empty queue, sender.rs:461-468, and send_segment arms only when it pushes), and here it
+ * is IDLE.
+ * The frame is built from the front entry e = q_first as it stands (an off / len a partial ACK moved included), sent
+ * whole even when it is longer than the connection's current mss (sender.rs:391: no repacketization): the 54 header
+ * bytes dk_tcp_tx_segment writes for this connection (ack / window from rx_conns[c] when given, else rcv_nxt /
+ * rcv_wnd_hdr; Ethernet / IPv4 from links[link], ip_word, the addresses and ports), seq = snd_una, flags ACK|PSH, or
+ * ACK|FIN when len == 0 (the end-of-send marker), payload src[off, off + len), the TCP checksum over it, or 0 under
+ * DK_TX_OFFLOAD_TCP. Frames are numbered in connection order; frame f owns slot f under dk_tcp_tx_layout's rule. No
+ * byte of out outside the frames is written. src and out must not overlap.
+ * State: q.tx_time[e] = DK_TCP_TX_TIME_NONE for both kinds (Karn, sender.rs:384-386). TIMEOUT additionally:
+ * rto = clamp(rto * 2.0, 0.1, 60.0) in f64, bit for bit; rtx_base_ns = now_ns; rtx_armed = 1. FAST leaves rto,
+ * rtx_base_ns and rtx_armed alone. Never written: tx_conns, q.off / q.len, every other pool entry, every other field
+ * of ack_conns.
+ * Capacity is all or nothing, tested on the device exactly as dk_tcp_tx_segment tests it: n_frames always reports the
+ * frames the call needs; if that exceeds max_frames, or n_frames * slot_stride exceeds out_bytes, no frame, no tx_time
+ * and no ack_conns field is written, the connections that had a frame report NO_ROOM and every frame[c] is 0xFFFFFFFF.
+ * Ordering against dk_tcp_ack_process and the queue append, which touch the same rows, is the caller's: they run on
+ * one stream. This entry point is additive: DK_RX_ABI_VERSION stays 4.
+ * ------------------------------------------------------------------------------------------------------------- */
+enum dk_tcp_rtx_fire { DK_TCP_RTX_NONE = 0, DK_TCP_RTX_TIMEOUT = 1, DK_TCP_RTX_FAST = 2 };
+
+enum dk_tcp_rtx_status {
+    DK_TCP_RTX_NOT_FIRED = 0,
+    DK_TCP_RTX_SENT = 1,      /* a frame was built                                                               */
+    DK_TCP_RTX_IDLE = 2,      /* nothing to resend (above): nothing changed                                      */
+    DK_TCP_RTX_E_FIRE = 3,    /* fire[c] > 2                                                                     */
+    DK_TCP_RTX_E_STATE = 4,   /* tx_conns[c].state != DK_TCP_ESTABLISHED                                         */
+    DK_TCP_RTX_E_QUEUE = 5,   /* q_first + q_count beyond the pool                                               */
+    DK_TCP_RTX_E_RANGE = 6,   /* the front's off + len beyond src_bytes                                          */
+    DK_TCP_RTX_E_SLOT = 7,    /* frame_lead + 54 + len > slot_stride, or len > 65,481                            */
+    DK_TCP_RTX_E_LINK = 8,    /* link >= nlinks                                                                  */
+    DK_TCP_RTX_E_WINDOW = 9,  /* the header window does not fit 16 bits (as dk_tcp_tx_segment judges it)         */
+    DK_TCP_RTX_NO_ROOM = 10   /* had a frame, but the call's frames do not fit: nothing of the call is done      */
+};
+
+/* Outputs (device). Per frame, [max_frames]: off_out, len_out (a dk_rx_batch over `out`), frame_conn (optional: the
+ * connection the frame belongs to). Per connection, [nconns]: status (enum dk_tcp_rtx_status), frame (the
+ * connection's frame index, 0xFFFFFFFF when it has none). n_frames: one word, the frames the call needs. */
+typedef struct dk_tcp_rtx_results {
+    uint32_t* off_out;
+    uint16_t* len_out;
+    uint32_t* frame_conn;
+    uint32_t* status;
+    uint32_t* frame;
+    uint32_t* n_frames;
+} dk_tcp_rtx_results;
+
+/* Asynchronous on `stream`; calls on one dk_tcp_tx_ctx (dk_tcp_retransmit and dk_tcp_tx_segment alike) are serialised.
+ * tx_conns, rx_conns (optional), the pool's off / len and fire are only read. nconns == 0 and an all-zero fire are
+ * valid calls that write n_frames = 0.
+ * Returns 0, EINVAL (a null required pointer, tx_conns / ack_conns / rx_conns not 16-byte aligned, src_bytes or
+ * out_bytes > DK_RX_MAX_BLOB, nlinks == 0), ENOMEM or EIO. */
+int dk_tcp_retransmit(dk_tcp_tx_ctx* ctx, const uint8_t* src, uint64_t src_bytes, const uint8_t* fire,
+                      const dk_tcp_tx_conn* tx_conns, dk_tcp_ack_conn* ack_conns, uint32_t nconns,
+                      const dk_tcp_conn* rx_conns, const dk_tcp_unacked* q, uint32_t nq, uint64_t now_ns,
+                      const dk_tx_link* links, uint32_t nlinks, uint8_t* out, uint64_t out_bytes,
+                      const dk_tcp_tx_layout* layout, uint32_t max_frames, uint32_t flags,
+                      const dk_tcp_rtx_results* results, void* stream);
 
 #ifdef __cplusplus
 }
