@@ -256,6 +256,34 @@ TCP_RTX_FUNCTIONS = [
                                   POINTER(DkTcpTxLayout), c_uint32, c_uint32, POINTER(DkTcpRtxResults), c_void_p]),
 ]
 
+# include/dk_tcp.h, the receiver's ACKs (dk_tcp_ack_emit, dk_tcp_ack_timer)
+TCP_ACKEMIT_STATUSES = ["OK", "E_STATE", "E_SND_NXT", "E_LINK", "E_WSCALE", "E_WINDOW", "E_SLOT", "NO_ROOM", "NOT_FIRED",
+                        "IDLE"]
+DK_TCP_ACKEMIT_NO_FRAME = 0xFFFFFFFF
+DACK_CONN_DTYPE = np.dtype([("armed", "<u4"), ("reserved", "<u4"), ("delay_ns", "<u8"), ("deadline_ns", "<u8"),
+                            ("reserved1", "<u8")])
+assert DACK_CONN_DTYPE.itemsize == 32
+TCP_ACKEMIT_RESULT_FIELDS = ["off_out", "len_out", "frame_conn", "frame_seg", "ack_frame", "status", "n_acks", "n_frames"]
+
+
+class DkTcpDackConn(ctypes.Structure):
+    _fields_ = [("armed", c_uint32), ("reserved", c_uint32), ("delay_ns", c_uint64), ("deadline_ns", c_uint64),
+                ("reserved1", c_uint64)]
+
+
+class DkTcpAckEmitResults(ctypes.Structure):
+    _fields_ = [(name, c_void_p) for name in TCP_ACKEMIT_RESULT_FIELDS]
+
+
+TCP_ACKEMIT_FUNCTIONS = [
+    ("dk_tcp_ack_emit", c_int, [c_void_p, POINTER(DkRxResults), c_uint32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                c_void_p, c_uint32, c_void_p, c_uint32, c_uint64, c_void_p, c_uint64,
+                                POINTER(DkTcpTxLayout), c_uint32, c_uint32, POINTER(DkTcpAckEmitResults), c_void_p]),
+    ("dk_tcp_ack_timer", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_uint32,
+                                 c_void_p, c_uint64, POINTER(DkTcpTxLayout), c_uint32, c_uint32,
+                                 POINTER(DkTcpAckEmitResults), c_void_p]),
+]
+
 # include/dk_diag.h (diagnostics, not the receive ABI)
 # include/dk_demi.h: delivered frames as demi_sgarray_t (host-side, no GPU work)
 class DemiSgaseg(ctypes.Structure):
@@ -307,15 +335,18 @@ DIAG_FUNCTIONS = [
     ("dk_diag_tcp_last_sort", c_int, [c_void_p]),
     ("dk_diag_tcp_ack_set_form", c_int, [c_void_p, c_int32]),
     ("dk_diag_tcp_ack_last_form", c_int, [c_void_p]),
+    ("dk_diag_tcp_ack_emit_set_form", c_int, [c_void_p, c_int32]),
+    ("dk_diag_tcp_ack_emit_last_form", c_int, [c_void_p]),
 ]
 DK_DIAG_RX_KNOBS = ["stage", "split", "small", "sched", "grid", "grid_per_cu", "debug", "lds_table", "tail", "udp_table",
                     "host_zc"]
 DK_TCP_WALKS = {"lane": 0, "wave": 1, "relay": 2, "scan": 3}
 DK_TCP_SORTS = {"counting": 0, "radix": 1}
 DK_TCP_ACK_FORMS = {"lane": 0, "wave": 1, "chip": 2}
+DK_TCP_ACK_EMIT_FORMS = {"lane": 0, "scan": 1}
 
 ALL_FUNCTIONS = (FUNCTIONS + RING_FUNCTIONS + TCP_FUNCTIONS + TCP_ACK_FUNCTIONS + TCP_TX_FUNCTIONS + TCP_RTX_FUNCTIONS +
-                 DIAG_FUNCTIONS +
+                 TCP_ACKEMIT_FUNCTIONS + DIAG_FUNCTIONS +
                  DEMI_FUNCTIONS + COMM_FUNCTIONS)
 
 _lib = None

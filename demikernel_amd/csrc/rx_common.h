@@ -250,6 +250,37 @@ struct TcpRtxEmitParams {
     uint32_t* frame_conn;  // nullable
 };
 
+// Pure ACKs (dk_tcp_ack_emit and dk_tcp_ack_timer, dk_tcp.h): the frame builder's view of what the plan kernels
+// (tcp_ackemit_kernels.hip) left. An item is a batch frame (dk_tcp_ack_emit) or a connection (dk_tcp_ack_timer).
+struct TcpAckEmitParams {
+    uint8_t* out;
+    uint64_t out_bytes;
+    const dk_tcp_tx_conn* tx;
+    const dk_tcp_conn* rx;
+    const dk_tx_link* links;
+    const uint64_t* first;      // [nitems] exclusive scan of the items' emit flags: an item's frame index
+    const uint64_t* total;      // the frames the call needs
+    const uint32_t* item_conn;  // [nitems] the item's connection; nullptr: the item is the connection
+    const uint32_t* item_ack;   // [nitems] RCV.NXT as the item's ACK carries it; nullptr: the table's receive_next
+    uint32_t nitems;
+    uint32_t stride, lead, max_frames, flags;
+    uint32_t* off_out;
+    uint16_t* len_out;
+    uint32_t* frame_conn;  // nullable
+    uint32_t* frame_seg;   // nullable: the item
+};
+// The connection-level checks of both calls, in dk_tcp.h's order: DK_TCP_ACKEMIT_OK or the failure.
+DK_HD uint32_t tcp_ackemit_check(const dk_tcp_tx_conn& T, const dk_tcp_conn& R, uint32_t nlinks, uint32_t stride,
+                                 uint32_t lead) {
+    if (T.state != DK_TCP_ESTABLISHED) return DK_TCP_ACKEMIT_E_STATE;
+    if (R.send_next != T.snd_nxt) return DK_TCP_ACKEMIT_E_SND_NXT;
+    if (T.link >= nlinks) return DK_TCP_ACKEMIT_E_LINK;
+    if (T.rcv_wscale > 14) return DK_TCP_ACKEMIT_E_WSCALE;
+    if ((R.buffer_size >> T.rcv_wscale) > 0xFFFFu) return DK_TCP_ACKEMIT_E_WINDOW;
+    if ((uint64_t)lead + 54u > stride) return DK_TCP_ACKEMIT_E_SLOT;
+    return DK_TCP_ACKEMIT_OK;
+}
+
 // TcpHeader::compute_size (tcp/header.rs:408-421) of an option list: 20 + the entries' sizes (TcpOptions2::compute_size
 // :43-54; a SACK entry's blocks must lie inside sack[]) + one EndOfOptionsList byte when the list is not empty, rounded
 // up to 4. 0 when the list cannot be serialized (more than 5 entries, unknown kind, SACK with 0 or > 4 blocks, more
@@ -300,3 +331,8 @@ int dk_launch_tx_serialize(const dk::TxSerParams& p, uint32_t grid, void* stream
 int dk_tcp_tx_emit_resident_blocks();  // occupancy of dk_tcp_tx_emit_kernel per CU (0 on error)
 int dk_launch_tcp_tx_emit(const dk::TcpTxEmitParams& p, uint32_t grid, void* stream);
 int dk_launch_tcp_rtx_emit(const dk::TcpRtxEmitParams& p, uint32_t grid, void* stream);
+int dk_launch_tcp_ack_emit(const dk::TcpAckEmitParams& p, uint32_t grid, void* stream);
+// The three-kernel exclusive scan of tcp_tx_kernels.hip over a[0 .. n) in place, its total to *tot; bsum holds
+// dk_tcp_tx_scan_tiles(n) words of scratch. 0 or EIO.
+uint32_t dk_tcp_tx_scan_tiles(uint32_t n);
+int dk_tcp_tx_scan(uint64_t* a, uint32_t n, uint64_t* bsum, uint64_t* tot, void* stream);

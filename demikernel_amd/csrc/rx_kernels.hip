@@ -2813,6 +2813,67 @@ __global__ __launch_bounds__(kBlock) void dk_tcp_rtx_emit_kernel(TcpRtxEmitParam
     }
 }
 
+// Pure ACKs (dk_tcp_ack_emit and dk_tcp_ack_timer, dk_tcp.h): ControlBlock::send_ack's frame, the 54 header bytes of the
+// kernels above with no payload behind them. Frame-major, one lane per frame: frame f belongs to the last item (a batch
+// frame, or a connection) holding the scan value f, found by binary search as dk_tcp_rtx_emit_kernel finds its
+// connection. seq = SND.NXT, flags ACK, ack = RCV.NXT as the item's moment left it, window = hdr_window_size() of that
+// RCV.NXT (ctrlblk.rs:699-720, :786-803).
+__global__ __launch_bounds__(kBlock) void dk_tcp_ack_emit_kernel(TcpAckEmitParams P) {
+    const uint64_t total = *P.total;
+    if (!tcp_tx_fits(total, P.max_frames, P.stride, P.out_bytes)) return;  // all or nothing, as the commit tests it
+    for (uint64_t f = (uint64_t)blockIdx.x * kBlock + threadIdx.x; f < total; f += (uint64_t)gridDim.x * kBlock) {
+        uint32_t lo = 0, hi = P.nitems;  // the last item whose frame index is <= f
+        while (hi - lo > 1) {
+            const uint32_t mid = lo + (hi - lo) / 2;
+            if (P.first[mid] <= f) lo = mid;
+            else hi = mid;
+        }
+        const uint32_t item = lo, conn = P.item_conn ? P.item_conn[item] : item;
+        const dk_tcp_tx_conn& T = P.tx[conn];
+        const dk_tcp_conn& R = P.rx[conn];
+        const uint32_t ack = P.item_ack ? P.item_ack[item] : R.receive_next;
+        const uint32_t seq = T.snd_nxt, b13 = 0x10u;
+        const uint32_t win = ((uint32_t)(R.buffer_size - (ack - R.reader_next)) >> (T.rcv_wscale & 31u)) & 0xFFFFu;
+        const uint32_t foff = (uint32_t)(f * P.stride + P.lead);
+        __builtin_nontemporal_store(foff, gptr(P.off_out) + f);
+        __builtin_nontemporal_store((uint16_t)54u, gptr(P.len_out) + f);
+        if (P.frame_conn) __builtin_nontemporal_store(conn, gptr(P.frame_conn) + f);
+        if (P.frame_seg) __builtin_nontemporal_store(item, gptr(P.frame_seg) + f);
+        const uint32_t src = T.local_ip, dst = T.remote_ip, ports = T.ports, ipw = T.ip_word;
+        const uint32_t* lw = reinterpret_cast<const uint32_t*>(P.links + T.link);
+        // the header arithmetic of dk_tcp_tx_emit_kernel with an empty payload
+        const uint32_t tot = 40u, seg = 20u;
+        const uint32_t ident = ipw & 0xFFFFu, ttl = (ipw >> 16) & 0xFFu, tos = ipw >> 24;
+        const uint32_t ipsum = (0x4500u | tos) + tot + ident + 0x4000u + ((ttl << 8) | 6u) + ip_be_sum(src) + ip_be_sum(dst);
+        const uint32_t ipc = csum_from_residue(mod_ffff(ipsum));
+        const uint32_t sport = ports & 0xFFFFu, dport = ports >> 16;
+        const uint32_t b12 = 5u << 4;
+        uint32_t c = 0;
+        if (!(P.flags & DK_TX_OFFLOAD_TCP)) {
+            const uint32_t be = ip_be_sum(src) + ip_be_sum(dst) + 6u + seg + sport + dport + be16_sum(seq) +
+                                be16_sum(ack) + ((b12 << 8) | b13) + win;
+            c = csum_from_residue(mod_ffff(be_residue(0u) + be));  // the payload's sum is 0
+        }
+        uint32_t d[14];
+        d[0] = lw[0];
+        d[1] = lw[1];
+        d[2] = lw[2];
+        d[3] = 0x0008u | 0x45u << 16 | tos << 24;
+        d[4] = bswap16(tot) | bswap16(ident) << 16;
+        d[5] = 0x0040u | ttl << 16 | 6u << 24;
+        d[6] = bswap16(ipc) | (src & 0xFFFFu) << 16;
+        d[7] = (src >> 16) | (dst & 0xFFFFu) << 16;
+        d[8] = (dst >> 16) | bswap16(sport) << 16;
+        const uint32_t sq = __builtin_bswap32(seq), ak = __builtin_bswap32(ack);
+        d[9] = bswap16(dport) | sq << 16;
+        d[10] = (sq >> 16) | ak << 16;
+        d[11] = (ak >> 16) | b12 << 16 | b13 << 24;
+        d[12] = bswap16(win) | bswap16(c) << 16;
+        d[13] = 0;
+        tx_store_header(P.out + foff, d, true);
+    }
+}
+
 }  // namespace
 }  // namespace dk
 
@@ -2948,5 +3009,11 @@ int dk_launch_tcp_tx_emit(const dk::TcpTxEmitParams& p, uint32_t grid, void* str
 int dk_launch_tcp_rtx_emit(const dk::TcpRtxEmitParams& p, uint32_t grid, void* stream) {
     if (p.nconns == 0 || grid == 0) return 0;
     hipLaunchKernelGGL(dk::dk_tcp_rtx_emit_kernel, dim3(grid), dim3(dk::kBlock), 0, (hipStream_t)stream, p);
+    return hipGetLastError() == hipSuccess ? 0 : 5;
+}
+
+int dk_launch_tcp_ack_emit(const dk::TcpAckEmitParams& p, uint32_t grid, void* stream) {
+    if (p.nitems == 0 || grid == 0) return 0;
+    hipLaunchKernelGGL(dk::dk_tcp_ack_emit_kernel, dim3(grid), dim3(dk::kBlock), 0, (hipStream_t)stream, p);
     return hipGetLastError() == hipSuccess ? 0 : 5;
 }

@@ -1772,12 +1772,13 @@ struct dk_tcp_ctx {
     bool ord_live = false;
     uint32_t ord_n = 0, ord_nconns = 0, ord_call = 0;
     dk_tcp_ack_state ack;
+    dk_tcp_emit_state emit;
 };
 
 int dk_tcp_ctx_order(dk_tcp_ctx* t, dk_tcp_order* o) {
     if (!t || !o) return EINVAL;
     *o = dk_tcp_order{t->device, t->svals, t->range, t->rec, t->ord_live, t->ord_n, t->ord_nconns, t->ord_call,
-                      t->last, &t->last_stream, &t->used, &t->ack};
+                      t->last, &t->last_stream, &t->used, &t->ack, &t->emit};
     return 0;
 }
 
@@ -1835,7 +1836,7 @@ void dk_tcp_ctx_destroy(dk_tcp_ctx* t) {
     for (void* p : {(void*)t->keys, (void*)t->skeys, (void*)t->svals, (void*)t->range, (void*)t->rec, (void*)t->temp,
                     (void*)t->cls, (void*)t->open_until, (void*)t->scan_sum, (void*)t->scan_post, (void*)t->scan_ends,
                     (void*)t->scan_idx, (void*)t->scan_rec,
-                    (void*)t->scan_head, (void*)t->shape, (void*)t->csort, t->ack.scratch})
+                    (void*)t->scan_head, (void*)t->shape, (void*)t->csort, t->ack.scratch, t->emit.scratch})
         if (p) (void)hipFree(p);
     if (t->shape_host) (void)hipHostFree(const_cast<uint32_t*>(t->shape_host));
     (void)hipEventDestroy(t->last);

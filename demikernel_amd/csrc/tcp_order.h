@@ -1,5 +1,5 @@
 // tcp_order.h — what a dk_tcp_rx_process call leaves in its context for the call that follows it on the same batch
-// (dk_tcp_ack_process, tcp_ack_kernels.hip): the batch's order by connection, still in the context's scratch, and the
+// (dk_tcp_ack_process, tcp_ack_kernels.hip; dk_tcp_ack_emit, tcp_ackemit_kernels.hip): the batch's order by connection, still in the context's scratch, and the
 // context's serialisation state. Internal to libdk_rx.so.
 #ifndef DK_TCP_ORDER_H
 #define DK_TCP_ORDER_H
@@ -18,6 +18,16 @@ struct dk_tcp_ack_state {
     size_t scratch_cap = 0;
 };
 
+// dk_tcp_ack_emit's own turn counter and scratch (freed by dk_tcp_ctx_destroy): it and dk_tcp_ack_process may both
+// follow one dk_tcp_rx_process call, in either order.
+struct dk_tcp_emit_state {
+    int form = -1;       // dk_diag_tcp_ack_emit_set_form: 0 lane, 1 wave, -1 the rule
+    int last_form = -1;  // the form the last dk_tcp_ack_emit call ran
+    uint32_t done = 0;   // the dk_tcp_rx_process call number the last dk_tcp_ack_emit call consumed
+    void* scratch = nullptr;
+    size_t scratch_cap = 0;
+};
+
 struct dk_tcp_order {
     int device;
     // connection c's walked segments are the frames svals[range[2c] .. range[2c + 1]), in arrival order (the segments
@@ -33,6 +43,7 @@ struct dk_tcp_order {
     hipStream_t* last_stream;
     bool* used;
     dk_tcp_ack_state* ack;
+    dk_tcp_emit_state* emit;
 };
 
 // 0, or EINVAL for a null context.

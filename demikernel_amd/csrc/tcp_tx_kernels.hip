@@ -1,5 +1,5 @@
-// tcp_tx_kernels.hip — dk_tcp_tx_segment and dk_tcp_retransmit (dk_tcp.h): the plan and commit kernels and the host
-// entry points. The emit kernels (the payload copy, the checksums and the headers) are dk_tcp_tx_emit_kernel and
+// tcp_tx_kernels.hip — dk_tcp_tx_segment, dk_tcp_retransmit and dk_tcp_ack_timer (dk_tcp.h): the plan and commit kernels
+// and the host entry points. The emit kernels (the payload copy, the checksums and the headers) are dk_tcp_tx_emit_kernel and
 // dk_tcp_rtx_emit_kernel in rx_kernels.hip, next to the dk_tx_serialize code they share their header arithmetic with.
 //
 // Sender::send_segment (tcp/established/sender.rs:124-208) cuts one segment at a time, each as large as
@@ -320,6 +320,53 @@ __global__ __launch_bounds__(kBlock) void rtx_commit(RtxPlan P) {
     }
 }
 
+// dk_tcp_ack_timer (dk_tcp.h): the acknowledger's expiry, with dk_tcp_retransmit's shape. One lane per connection
+// plans (the checks in the header's order, emit 0/1), the scan numbers the frames, dk_tcp_ack_emit_kernel
+// (rx_kernels.hip) builds them from the tables as they stand, and one lane per connection commits behind the same
+// capacity test.
+struct AckTimerPlan {
+    uint64_t out_bytes;
+    const uint8_t* fire;
+    const dk_tcp_tx_conn* tx;
+    const dk_tcp_conn* rx;
+    dk_tcp_dack_conn* dack;
+    uint32_t nconns, nlinks;
+    uint32_t stride, lead, max_frames;
+    uint64_t* emit;  // [nconns] emit flags, then their exclusive scan
+    uint64_t* tot;   // the frames the call needs
+    dk_tcp_ackemit_results res;
+};
+
+__global__ __launch_bounds__(kBlock) void ack_timer_plan(AckTimerPlan P) {
+    const uint32_t c = blockIdx.x * kBlock + threadIdx.x;
+    if (c >= P.nconns) return;
+    uint32_t st = DK_TCP_ACKEMIT_NOT_FIRED;
+    if (P.fire[c]) {
+        st = dk::tcp_ackemit_check(P.tx[c], P.rx[c], P.nlinks, P.stride, P.lead);
+        if (st == DK_TCP_ACKEMIT_OK && !P.dack[c].armed) st = DK_TCP_ACKEMIT_IDLE;
+    }
+    P.emit[c] = st == DK_TCP_ACKEMIT_OK;
+    P.res.status[c] = st;  // OK stands unless ack_timer_commit finds no room
+}
+
+__global__ __launch_bounds__(kBlock) void ack_timer_commit(AckTimerPlan P) {
+    const uint32_t c = blockIdx.x * kBlock + threadIdx.x;
+    if (c >= P.nconns) return;
+    const uint64_t total = P.tot[0];
+    const bool fits = dk::tcp_tx_fits(total, P.max_frames, P.stride, P.out_bytes);
+    if (c == 0) *P.res.n_frames = (uint32_t)total;  // at most nconns
+    const uint64_t first = P.emit[c];
+    const bool emits = (c + 1 < P.nconns ? P.emit[c + 1] : total) != first;
+    P.res.ack_frame[c] = emits && fits ? (uint32_t)first : 0xFFFFFFFFu;
+    P.res.n_acks[c] = emits;
+    if (!emits) return;
+    if (!fits) {
+        P.res.status[c] = DK_TCP_ACKEMIT_NO_ROOM;
+        return;
+    }
+    P.dack[c].armed = 0;  // emit() clears the deadline (ctrlblk.rs:761); deadline_ns is left as it is
+}
+
 struct DeviceGuard {
     int prev = -1;
     explicit DeviceGuard(int dev) {
@@ -375,7 +422,16 @@ struct dk_tcp_tx_ctx {
     uint64_t* rtx_emit = nullptr;
     uint4* rtx_rec = nullptr;
     size_t rtx_emit_cap = 0, rtx_rec_cap = 0;
+    // dk_tcp_ack_timer's emit flags / their scan per connection (tot[4] is its total)
+    uint64_t* ackt_emit = nullptr;
+    size_t ackt_emit_cap = 0;
 };
+
+uint32_t dk_tcp_tx_scan_tiles(uint32_t n) { return (n + dk_tcp_tx::kTile - 1) / dk_tcp_tx::kTile; }
+
+int dk_tcp_tx_scan(uint64_t* a, uint32_t n, uint64_t* bsum, uint64_t* tot, void* stream) {
+    return dk_tcp_tx::scan(a, nullptr, n, bsum, dk_tcp_tx_scan_tiles(n), tot, nullptr, (hipStream_t)stream);
+}
 
 extern "C" {
 
@@ -401,7 +457,7 @@ int dk_tcp_tx_ctx_create(int32_t device, dk_tcp_tx_ctx** out) {
         delete t;
         return EINVAL;
     }
-    if (dk_tcp_tx::grow(t->tot, t->tot_cap, 4)) {
+    if (dk_tcp_tx::grow(t->tot, t->tot_cap, 5)) {
         (void)hipEventDestroy(t->last);
         delete t;
         return ENOMEM;
@@ -415,7 +471,8 @@ void dk_tcp_tx_ctx_destroy(dk_tcp_tx_ctx* t) {
     dk_tcp_tx::DeviceGuard g(t->device);
     if (t->used) (void)hipEventSynchronize(t->last);
     for (void* p : {(void*)t->seqsp, (void*)t->flags, (void*)t->frames, (void*)t->bsum, (void*)t->tot, (void*)t->head,
-                    (void*)t->tail, (void*)t->rec, (void*)t->cm, (void*)t->rtx_emit, (void*)t->rtx_rec})
+                    (void*)t->tail, (void*)t->rec, (void*)t->cm, (void*)t->rtx_emit, (void*)t->rtx_rec,
+                    (void*)t->ackt_emit})
         if (p) (void)hipFree(p);
     (void)hipEventDestroy(t->last);
     delete t;
@@ -525,6 +582,50 @@ int dk_tcp_retransmit(dk_tcp_tx_ctx* t, const uint8_t* src, uint64_t src_bytes, 
         const uint32_t grid = std::min<uint32_t>(std::min(max_frames, nconns) / 256 + 1, std::min(t->occ, 8u) * t->cus);
         if (max_frames && dk_launch_tcp_rtx_emit(E, grid, s)) return EIO;
         hipLaunchKernelGGL(rtx_commit, per_conn, dim3(kBlock), 0, s, P);
+        if (hipGetLastError() != hipSuccess) return EIO;
+    }
+    if (hipEventRecord(t->last, s) != hipSuccess) return EIO;
+    t->last_stream = s;
+    t->used = true;
+    return 0;
+}
+
+int dk_tcp_ack_timer(dk_tcp_tx_ctx* t, const uint8_t* fire, const dk_tcp_tx_conn* tx_conns, const dk_tcp_conn* rx_conns,
+                     dk_tcp_dack_conn* dack, uint32_t nconns, const dk_tx_link* links, uint32_t nlinks, uint8_t* out,
+                     uint64_t out_bytes, const dk_tcp_tx_layout* layout, uint32_t max_frames, uint32_t flags,
+                     const dk_tcp_ackemit_results* res, void* stream) {
+    using namespace dk_tcp_tx;
+    if (!t || !layout || !res || !res->n_frames || !links || nlinks == 0) return EINVAL;
+    if (out_bytes > DK_RX_MAX_BLOB) return EINVAL;
+    if ((reinterpret_cast<uintptr_t>(tx_conns) | reinterpret_cast<uintptr_t>(rx_conns) |
+         reinterpret_cast<uintptr_t>(dack)) & 15)
+        return EINVAL;
+    if (nconns && (!fire || !tx_conns || !rx_conns || !dack || !res->status || !res->n_acks || !res->ack_frame))
+        return EINVAL;
+    if (nconns && max_frames && (!out || !res->off_out || !res->len_out)) return EINVAL;
+    DeviceGuard g(t->device);
+    const hipStream_t s = (hipStream_t)stream;
+    if (t->used && t->last_stream != s && hipStreamWaitEvent(s, t->last, 0) != hipSuccess) return EIO;
+    if (nconns == 0) {
+        if (hipMemsetAsync(res->n_frames, 0, sizeof(uint32_t), s) != hipSuccess) return EIO;
+    } else {
+        const uint32_t nb = (nconns + kTile - 1) / kTile;
+        const bool grows = t->ackt_emit_cap < nconns || t->bsum_cap < nb;
+        if (t->used && grows && hipEventSynchronize(t->last) != hipSuccess) return EIO;  // in-flight work on the scratch
+        int rc = 0;
+        if ((rc = grow(t->ackt_emit, t->ackt_emit_cap, nconns)) || (rc = grow(t->bsum, t->bsum_cap, nb))) return rc;
+        AckTimerPlan P{out_bytes, fire, tx_conns, rx_conns, dack, nconns, nlinks, layout->slot_stride, layout->frame_lead,
+                       max_frames, t->ackt_emit, t->tot + 4, *res};
+        const dim3 per_conn((nconns + kBlock - 1) / kBlock);
+        hipLaunchKernelGGL(ack_timer_plan, per_conn, dim3(kBlock), 0, s, P);
+        if ((rc = scan(t->ackt_emit, nullptr, nconns, t->bsum, nb, t->tot + 4, nullptr, s))) return rc;
+        // emit reads the tables, never the rows the commit writes, and runs first
+        dk::TcpAckEmitParams E{out, out_bytes, tx_conns, rx_conns, links, t->ackt_emit, t->tot + 4, nullptr, nullptr,
+                               nconns, layout->slot_stride, layout->frame_lead, max_frames, flags, res->off_out,
+                               res->len_out, res->frame_conn, nullptr};
+        const uint32_t grid = std::min<uint32_t>(std::min(max_frames, nconns) / 256 + 1, 8u * t->cus);
+        if (max_frames && dk_launch_tcp_ack_emit(E, grid, s)) return EIO;
+        hipLaunchKernelGGL(ack_timer_commit, per_conn, dim3(kBlock), 0, s, P);
         if (hipGetLastError() != hipSuccess) return EIO;
     }
     if (hipEventRecord(t->last, s) != hipSuccess) return EIO;

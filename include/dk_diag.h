@@ -86,6 +86,12 @@ int dk_diag_tcp_ack_set_form(struct dk_tcp_ctx* ctx, int32_t form);
 /* The form the context's last dk_tcp_ack_process call ran (0 lane, 1 wave, 2 chip; -1 none yet, or a call with no
  * table rows). */
 int dk_diag_tcp_ack_last_form(const struct dk_tcp_ctx* ctx);
+/* Which form dk_tcp_ack_emit runs (dk_tcp.h): form -1 the engine's rule, 0 one lane per connection, 1 the scan form.
+ * Returns 0 or EINVAL. */
+int dk_diag_tcp_ack_emit_set_form(struct dk_tcp_ctx* ctx, int32_t form);
+/* The form the context's last dk_tcp_ack_emit call ran (0 lane, 1 scan; -1 none yet, or a call with no segments or no
+ * table rows). */
+int dk_diag_tcp_ack_emit_last_form(const struct dk_tcp_ctx* ctx);
 
 #ifdef __cplusplus
 }

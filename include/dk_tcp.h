@@ -18,8 +18,9 @@
  * The sender's reaction to the ACKs those segments carry (SND.UNA, the send window, the unacknowledged queue, the RTT
  * estimate and the retransmit deadline) is dk_tcp_ack_process and cutting pushed buffers into segments is
  * dk_tcp_tx_segment, both below; resending the front of the unacknowledged queue (retransmit() and the timeout's
- * back-off) is dk_tcp_retransmit, at the end.
- * Not modelled: the delayed-ACK timer and the ACKs segments trigger, congestion control (on_ack_received,
+ * back-off) is dk_tcp_retransmit; the ACKs the segments trigger and the delayed-ACK timer are dk_tcp_ack_emit and
+ * dk_tcp_ack_timer, at the end.
+ * Not modelled: congestion control (on_ack_received,
  * on_rto and on_fast_retransmit: the host replays them from dk_tcp_ack_out and from what it fires), deciding which
  * retransmit timers have expired (the host compares rtx_base_ns + rto with its clock and names the connections in
  * dk_tcp_retransmit's fire[]), states other than ESTABLISHED (FIN-WAIT-1/2 etc.).
@@ -407,6 +408,119 @@ int dk_tcp_retransmit(dk_tcp_tx_ctx* ctx, const uint8_t* src, uint64_t src_bytes
                       const dk_tx_link* links, uint32_t nlinks, uint8_t* out, uint64_t out_bytes,
                       const dk_tcp_tx_layout* layout, uint32_t max_frames, uint32_t flags,
                       const dk_tcp_rtx_results* results, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * The receiver's ACKs: what ControlBlock::process_packet (ctrlblk.rs:403-440) decides per segment and send_ack
+ * (:712-720, tcp_header :699-709, emit :723-776) sends, for every connection of a batch at once, and the delayed-ACK
+ * timer's expiry (background/acknowledger.rs). An ACK is a frame of 54 bytes, no payload and no options: exactly what
+ * dk_tcp_tx_segment would write for the connection with an empty payload (Ethernet / IPv4 from links[link], ip_word,
+ * the addresses and ports; IPv4 total length 40; both checksums filled, the TCP checksum 0 under DK_TX_OFFLOAD_TCP;
+ * no padding), flags ACK, seq = tx_conns[c].snd_nxt, ack = RCV.NXT and window = (buffer_size - (RCV.NXT -
+ * reader_next)) >> rcv_wscale, both as they stood when the ACK was sent: after the segment that triggered it, not at
+ * the end of the batch. reader_next, buffer_size and SND.NXT do not move during a call.
+ * Per segment of a connection, in arrival order, by the action dk_tcp_rx_process gave it (armed =
+ * receive_ack_deadline_time_secs.is_some()):
+ *   DELIVERED, NO_DATA       an ACK only if armed; armed toggles: 0 -> 1 with deadline_ns = now_ns + delay_ns, 1 -> 0
+ *                            (ctrlblk.rs:426-437)
+ *   STORED, STORE_DUP        an ACK; armed = 1, deadline_ns = now_ns + delay_ns (:680-682 sends and clears, then
+ *                            :426-431 finds the deadline None and arms it: the reference's quirk, kept)
+ *   FIN                      an ACK, after RCV.NXT moved over the FIN; armed = 0 (:1011-1016 returns before the toggle)
+ *   DUPLICATE, OUT_OF_WINDOW an ACK and armed = 0, unless the segment has RST set: then nothing (:495-501, :525-531)
+ *   ACK_UNSENT               an ACK; armed = 0 (:640-646)
+ *   RST, SYN, NO_ACK, UNPROCESSED, SKIP: nothing (:570-613, :355-363)
+ * deadline_ns is left as it is when armed is cleared; a connection none of whose segments touched armed keeps its row
+ * byte for byte. `now_ns` is one value per call. armed != 0 counts as armed; 0 or 1 is written.
+ * RCV.NXT at a segment is not in the table after the call, but it moves only at DELIVERED and FIN segments, and those
+ * start exactly at RCV.NXT once their front is trimmed: RCV.NXT after frame i is the trimmed start (seq + the view's
+ * offset into the payload + 1 for a trimmed SYN) of the connection's next DELIVERED / FIN frame, the table's
+ * receive_next when there is none. The pass needs that call's action and view, and the order it left in the context.
+ * Connection-level failures, the first that applies, in this order (the connection's row is untouched, nothing is
+ * emitted for it, n_acks 0):
+ *   E_STATE    tx_conns[c].state != DK_TCP_ESTABLISHED
+ *   E_SND_NXT  rx_conns[c].send_next != tx_conns[c].snd_nxt
+ *   E_LINK     link >= nlinks
+ *   E_WSCALE   rcv_wscale > 14
+ *   E_WINDOW   buffer_size >> rcv_wscale > 0xFFFF: the full-open window is what hdr_window_size would panic on, and
+ *              judged this way the check does not depend on where RCV.NXT stood (a table whose RCV.NXT - reader_next
+ *              exceeds buffer_size gets the low 16 bits of the wrapped difference)
+ *   E_SLOT     frame_lead + 54 > slot_stride
+ * Frames are numbered in the order of the batch frames that triggered them (dk_tcp_ack_timer: in connection order),
+ * so a connection's ACKs are in arrival order; frame f owns slot f under dk_tcp_tx_layout's rule. No byte of out
+ * outside the frames is written. Capacity is all or nothing, tested on the device as dk_tcp_tx_segment tests it:
+ * n_frames always reports the frames the call needs; if that exceeds max_frames, or n_frames * slot_stride exceeds
+ * out_bytes, no frame and no dack field is written, ack_frame is 0xFFFFFFFF everywhere and the connections that had
+ * frames report NO_ROOM (n_acks still holds their need). Such a dk_tcp_ack_emit call has taken its turn all the same
+ * (the test is made on the device): n slots are the most a batch can need. Nothing but dack, the frames and the
+ * outputs is ever written.
+ * Not modelled: clearing armed when a data frame of the connection piggybacks the ACK (emit, :761):
+ * dk_tcp_tx_segment and dk_tcp_retransmit do not touch dack, which costs one redundant pure ACK per delay.
+ * These entry points are additive: DK_RX_ABI_VERSION stays 4.
+ * ------------------------------------------------------------------------------------------------------------- */
+/* The delayed-ACK state of one connection, indexed by flow id. Device memory, 16-byte aligned, updated in place. */
+typedef struct dk_tcp_dack_conn {
+    uint32_t armed;        /* receive_ack_deadline_time_secs is Some                                              */
+    uint32_t reserved;
+    uint64_t delay_ns;     /* receive_ack_delay_timeout_secs (input)                                              */
+    uint64_t deadline_ns;  /* now_ns + delay_ns (wrapping) of the call that armed it last                         */
+    uint64_t reserved1;
+} dk_tcp_dack_conn;        /* 32 bytes */
+
+enum dk_tcp_ackemit_status {
+    DK_TCP_ACKEMIT_OK = 0,         /* dk_tcp_ack_timer: the ACK was sent                                          */
+    DK_TCP_ACKEMIT_E_STATE = 1,
+    DK_TCP_ACKEMIT_E_SND_NXT = 2,
+    DK_TCP_ACKEMIT_E_LINK = 3,
+    DK_TCP_ACKEMIT_E_WSCALE = 4,
+    DK_TCP_ACKEMIT_E_WINDOW = 5,
+    DK_TCP_ACKEMIT_E_SLOT = 6,
+    DK_TCP_ACKEMIT_NO_ROOM = 7,    /* had frames, but the call's frames do not fit: nothing of the call is done   */
+    DK_TCP_ACKEMIT_NOT_FIRED = 8,  /* dk_tcp_ack_timer: fire[c] == 0                                              */
+    DK_TCP_ACKEMIT_IDLE = 9        /* dk_tcp_ack_timer: armed == 0, nothing changed                               */
+};
+
+/* Outputs (device). Per frame, [max_frames]: off_out, len_out (a dk_rx_batch over `out`), frame_conn (optional: the
+ * frame's connection), frame_seg (optional, dk_tcp_ack_emit only: the batch frame that triggered it). ack_frame: per
+ * batch frame [n] (dk_tcp_ack_emit) or per connection [nconns] (dk_tcp_ack_timer), its ACK's frame index or
+ * 0xFFFFFFFF. Per connection, [nconns]: status (enum dk_tcp_ackemit_status), n_acks (the ACKs it needs). n_frames:
+ * one word, the frames the call needs. */
+typedef struct dk_tcp_ackemit_results {
+    uint32_t* off_out;
+    uint16_t* len_out;
+    uint32_t* frame_conn;
+    uint32_t* frame_seg;
+    uint32_t* ack_frame;
+    uint32_t* status;
+    uint32_t* n_acks;
+    uint32_t* n_frames;
+} dk_tcp_ackemit_results;
+
+/* Follows the dk_tcp_rx_process call of the same ctx, with that call's rx (flow_id is required), n and nconns, `action`
+ * and `view` that call's dk_tcp_out arrays and rx_conns its table, as dk_tcp_ack_process does. It keeps a turn counter
+ * of its own: dk_tcp_ack_emit and dk_tcp_ack_process may both follow one dk_tcp_rx_process call, in either order, with
+ * identical results; a second dk_tcp_ack_emit on the same call, a call out of turn or one with another n / nconns
+ * returns EINVAL and writes nothing. rx_conns and tx_conns are only read. Asynchronous on `stream`, serialised with
+ * the context's other calls as they are. The engine runs one lane per connection (the specification in code); at >= 8
+ * segments per connection the scan form (the armed bit and the RCV.NXT of each moment as two scans over the whole
+ * batch in its order by connection); dk_diag_tcp_ack_emit_set_form (dk_diag.h) forces a form. Results are identical;
+ * the frames are written frame-major in both. The environment is never read.
+ * Returns 0, EINVAL (also: a null required pointer, rx_conns / tx_conns / dack not 16-byte aligned, out_bytes >
+ * DK_RX_MAX_BLOB, nlinks == 0), ENOMEM or EIO. */
+int dk_tcp_ack_emit(dk_tcp_ctx* ctx, const dk_rx_results* rx, uint32_t n, const uint8_t* action,
+                    const dk_tcp_view* view, const dk_tcp_conn* rx_conns, const dk_tcp_tx_conn* tx_conns,
+                    dk_tcp_dack_conn* dack, uint32_t nconns, const dk_tx_link* links, uint32_t nlinks, uint64_t now_ns,
+                    uint8_t* out, uint64_t out_bytes, const dk_tcp_tx_layout* layout, uint32_t max_frames,
+                    uint32_t flags, const dk_tcp_ackemit_results* results, void* stream);
+
+/* The acknowledger's expiry: fire[0 .. nconns) is a device array the host fills, nonzero for a connection whose
+ * deadline_ns has passed on its clock. Per fired connection, in connection order: the connection-level checks above,
+ * then armed == 0 is IDLE and changes nothing, else one ACK from the tables as they stand (rx_conns is required) and
+ * armed = 0. The frames come from the same device builder as dk_tcp_ack_emit's; the capacity rule is the same;
+ * results->frame_seg is not used. A call on dk_tcp_tx_ctx, serialised as dk_tcp_retransmit is. nconns == 0 and an
+ * all-zero fire are valid calls that write n_frames = 0. Returns 0, EINVAL, ENOMEM or EIO as above. */
+int dk_tcp_ack_timer(dk_tcp_tx_ctx* ctx, const uint8_t* fire, const dk_tcp_tx_conn* tx_conns,
+                     const dk_tcp_conn* rx_conns, dk_tcp_dack_conn* dack, uint32_t nconns, const dk_tx_link* links,
+                     uint32_t nlinks, uint8_t* out, uint64_t out_bytes, const dk_tcp_tx_layout* layout,
+                     uint32_t max_frames, uint32_t flags, const dk_tcp_ackemit_results* results, void* stream);
 
 #ifdef __cplusplus
 }
