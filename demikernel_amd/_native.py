@@ -284,6 +284,41 @@ TCP_ACKEMIT_FUNCTIONS = [
                                  POINTER(DkTcpAckEmitResults), c_void_p]),
 ]
 
+# include/dk_tcp.h, congestion control and timer expiry (dk_tcp_cc_ack, dk_tcp_timers, dk_tcp_cc_send)
+TCP_CC_STATUSES = ["OK", "E_STATE", "E_SND_NXT", "E_MSS", "E_RTO"]
+DK_TCP_CC_OK, DK_TCP_CC_E_STATE, DK_TCP_CC_E_SND_NXT, DK_TCP_CC_E_MSS, DK_TCP_CC_E_RTO = range(5)
+TCP_CC_FLAGS = {"CUBIC": 1, "FAST_CONVERGENCE": 2, "IN_RECOVERY": 4, "LAST_WAS_RTO": 8, "RETRANSMIT_NOW": 16}
+DK_TCP_CC_BEFORE_SEND, DK_TCP_CC_AFTER_SEND = range(2)
+CC_CONN_U32 = ["flags", "cwnd", "ssthresh", "w_max", "initial_cwnd", "ltci", "dup_acks", "rpif", "recover", "prev_ack"]
+CC_CONN_U64 = ["ca_start_ns", "last_send_ns", "rtt_at_last_send_ns"]
+CC_CONN_DTYPE = np.dtype([(k, "<u4") for k in CC_CONN_U32] + [(k, "<u8") for k in CC_CONN_U64])
+assert CC_CONN_DTYPE.itemsize == 64
+TCP_CC_ACK_OUT_FIELDS = ["status", "new_acks", "dup_acks", "cwnd_after"]
+TCP_TIMERS_OUT_FIELDS = ["status", "n_fast", "n_timeout", "n_ack"]
+
+
+class DkTcpCcConn(ctypes.Structure):
+    _fields_ = [(k, c_uint32) for k in CC_CONN_U32] + [(k, c_uint64) for k in CC_CONN_U64]
+
+
+class DkTcpCcAckOut(ctypes.Structure):
+    _fields_ = [(name, c_void_p) for name in TCP_CC_ACK_OUT_FIELDS]
+
+
+class DkTcpTimersOut(ctypes.Structure):
+    _fields_ = [(name, c_void_p) for name in TCP_TIMERS_OUT_FIELDS]
+
+
+TCP_CC_FUNCTIONS = [
+    ("dk_tcp_rto_ns", c_uint64, [ctypes.c_double]),
+    ("dk_tcp_cc_ack", c_int, [c_void_p, POINTER(DkRxResults), c_uint32, c_void_p, c_void_p, c_void_p, c_void_p,
+                              c_void_p, c_uint32, c_uint64, POINTER(DkTcpCcAckOut), c_void_p]),
+    ("dk_tcp_timers", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_uint64, c_void_p,
+                              c_void_p, POINTER(DkTcpTimersOut), c_void_p]),
+    ("dk_tcp_cc_send", c_int, [c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_uint32, POINTER(DkTcpTxPush),
+                               c_uint32, POINTER(DkTcpTxResults), c_uint64, c_void_p, c_void_p]),
+]
+
 # include/dk_diag.h (diagnostics, not the receive ABI)
 # include/dk_demi.h: delivered frames as demi_sgarray_t (host-side, no GPU work)
 class DemiSgaseg(ctypes.Structure):
@@ -337,6 +372,7 @@ DIAG_FUNCTIONS = [
     ("dk_diag_tcp_ack_last_form", c_int, [c_void_p]),
     ("dk_diag_tcp_ack_emit_set_form", c_int, [c_void_p, c_int32]),
     ("dk_diag_tcp_ack_emit_last_form", c_int, [c_void_p]),
+    ("dk_diag_tcp_cc_cbrt", c_int, [c_void_p, c_void_p, c_uint32, c_void_p]),
 ]
 DK_DIAG_RX_KNOBS = ["stage", "split", "small", "sched", "grid", "grid_per_cu", "debug", "lds_table", "tail", "udp_table",
                     "host_zc"]
@@ -346,7 +382,7 @@ DK_TCP_ACK_FORMS = {"lane": 0, "wave": 1, "chip": 2}
 DK_TCP_ACK_EMIT_FORMS = {"lane": 0, "scan": 1}
 
 ALL_FUNCTIONS = (FUNCTIONS + RING_FUNCTIONS + TCP_FUNCTIONS + TCP_ACK_FUNCTIONS + TCP_TX_FUNCTIONS + TCP_RTX_FUNCTIONS +
-                 TCP_ACKEMIT_FUNCTIONS + DIAG_FUNCTIONS +
+                 TCP_ACKEMIT_FUNCTIONS + TCP_CC_FUNCTIONS + DIAG_FUNCTIONS +
                  DEMI_FUNCTIONS + COMM_FUNCTIONS)
 
 _lib = None

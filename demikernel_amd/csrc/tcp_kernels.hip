@@ -1773,12 +1773,13 @@ struct dk_tcp_ctx {
     uint32_t ord_n = 0, ord_nconns = 0, ord_call = 0;
     dk_tcp_ack_state ack;
     dk_tcp_emit_state emit;
+    dk_tcp_cc_state cc;
 };
 
 int dk_tcp_ctx_order(dk_tcp_ctx* t, dk_tcp_order* o) {
     if (!t || !o) return EINVAL;
     *o = dk_tcp_order{t->device, t->svals, t->range, t->rec, t->ord_live, t->ord_n, t->ord_nconns, t->ord_call,
-                      t->last, &t->last_stream, &t->used, &t->ack, &t->emit};
+                      t->last, &t->last_stream, &t->used, &t->ack, &t->emit, &t->cc};
     return 0;
 }
 

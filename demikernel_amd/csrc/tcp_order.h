@@ -1,5 +1,6 @@
 // tcp_order.h — what a dk_tcp_rx_process call leaves in its context for the call that follows it on the same batch
-// (dk_tcp_ack_process, tcp_ack_kernels.hip; dk_tcp_ack_emit, tcp_ackemit_kernels.hip): the batch's order by connection, still in the context's scratch, and the
+// (dk_tcp_ack_process, tcp_ack_kernels.hip; dk_tcp_ack_emit, tcp_ackemit_kernels.hip; dk_tcp_cc_ack,
+// tcp_cc_kernels.hip): the batch's order by connection, still in the context's scratch, and the
 // context's serialisation state. Internal to libdk_rx.so.
 #ifndef DK_TCP_ORDER_H
 #define DK_TCP_ORDER_H
@@ -28,6 +29,12 @@ struct dk_tcp_emit_state {
     size_t scratch_cap = 0;
 };
 
+// dk_tcp_cc_ack's turn counter (tcp_cc_kernels.hip): it follows a dk_tcp_rx_process call as the two above do, once, and
+// before that call's dk_tcp_ack_process.
+struct dk_tcp_cc_state {
+    uint32_t done = 0;   // the dk_tcp_rx_process call number the last dk_tcp_cc_ack call consumed
+};
+
 struct dk_tcp_order {
     int device;
     // connection c's walked segments are the frames svals[range[2c] .. range[2c + 1]), in arrival order (the segments
@@ -44,9 +51,23 @@ struct dk_tcp_order {
     bool* used;
     dk_tcp_ack_state* ack;
     dk_tcp_emit_state* emit;
+    dk_tcp_cc_state* cc;
 };
 
 // 0, or EINVAL for a null context.
 int dk_tcp_ctx_order(dk_tcp_ctx* ctx, dk_tcp_order* out);
+
+// The serialisation state of a dk_tcp_tx_ctx (tcp_tx_kernels.hip), for the calls on it that live in other files
+// (dk_tcp_timers, dk_tcp_cc_send: tcp_cc_kernels.hip). They use no scratch of the context.
+struct dk_tcp_tx_ctx;
+struct dk_tcp_tx_serial {
+    int device;
+    hipEvent_t last;
+    hipStream_t* last_stream;
+    bool* used;
+};
+
+// 0, or EINVAL for a null context.
+int dk_tcp_tx_ctx_serial(dk_tcp_tx_ctx* ctx, dk_tcp_tx_serial* out);
 
 #endif  // DK_TCP_ORDER_H

@@ -29,6 +29,7 @@
 #include "../../include/dk_diag.h"
 #include "../../include/dk_tcp.h"
 #include "rx_common.h"
+#include "tcp_order.h"
 
 namespace dk_tcp_tx {
 namespace {
@@ -426,6 +427,12 @@ struct dk_tcp_tx_ctx {
     uint64_t* ackt_emit = nullptr;
     size_t ackt_emit_cap = 0;
 };
+
+int dk_tcp_tx_ctx_serial(dk_tcp_tx_ctx* t, dk_tcp_tx_serial* o) {
+    if (!t || !o) return EINVAL;
+    *o = dk_tcp_tx_serial{t->device, t->last, &t->last_stream, &t->used};
+    return 0;
+}
 
 uint32_t dk_tcp_tx_scan_tiles(uint32_t n) { return (n + dk_tcp_tx::kTile - 1) / dk_tcp_tx::kTile; }
 

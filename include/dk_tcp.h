@@ -20,10 +20,10 @@
  * dk_tcp_tx_segment, both below; resending the front of the unacknowledged queue (retransmit() and the timeout's
  * back-off) is dk_tcp_retransmit; the ACKs the segments trigger and the delayed-ACK timer are dk_tcp_ack_emit and
  * dk_tcp_ack_timer, at the end.
- * Not modelled: congestion control (on_ack_received,
- * on_rto and on_fast_retransmit: the host replays them from dk_tcp_ack_out and from what it fires), deciding which
- * retransmit timers have expired (the host compares rtx_base_ns + rto with its clock and names the connections in
- * dk_tcp_retransmit's fire[]), states other than ESTABLISHED (FIN-WAIT-1/2 etc.).
+ * Congestion control (CUBIC's on_ack_received, on_rto, on_fast_retransmit and its two send hooks) and deciding which
+ * timers have expired are dk_tcp_cc_ack, dk_tcp_timers and dk_tcp_cc_send, the last section: where the sections
+ * between say that cwnd is an input or that the host fills fire[], those calls are what computes them on the device.
+ * Not modelled: states other than ESTABLISHED (FIN-WAIT-1/2 etc.), the persist timer, repacketization.
  *
  * Conventions as dk_rx.h: 0 or a positive errno; device pointers; asynchronous on the caller's stream. A context holds
  * one set of scratch buffers: calls on one context are serialised — a call on another stream than the previous call
@@ -521,6 +521,166 @@ int dk_tcp_ack_timer(dk_tcp_tx_ctx* ctx, const uint8_t* fire, const dk_tcp_tx_co
                      const dk_tcp_conn* rx_conns, dk_tcp_dack_conn* dack, uint32_t nconns, const dk_tx_link* links,
                      uint32_t nlinks, uint8_t* out, uint64_t out_bytes, const dk_tcp_tx_layout* layout,
                      uint32_t max_frames, uint32_t flags, const dk_tcp_ackemit_results* results, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Congestion control and timer expiry: CUBIC as established/congestion_control/cubic.rs states it (the reference's
+ * default algorithm), called as ControlBlock::process_ack calls it (ctrlblk.rs:622-630: on_ack_received for every
+ * segment that reaches process_ack, before the ack_num <= SND.NXT test), as Sender::send_segment calls it
+ * (sender.rs:124-177: on_cwnd_check_before_send, then on_send with the bytes in flight) and as
+ * background_retransmitter calls it (sender.rs:320-364: the retransmit_now flag and on_fast_retransmit, the deadline
+ * and on_rto), for every connection of a table at once. With these the "Not modelled" list at the top of this file
+ * and dk_tcp_retransmit's "deciding who fires stays with the host" are superseded: tx_conns[c].cwnd and fire[] are
+ * computed on the device.
+ *
+ * Arithmetic, bit for bit:
+ *   u32 arithmetic wraps, as in the reference's release build (the debug build's overflow panics are not modelled);
+ *     saturating_sub saturates. Sequence comparisons take the sign of the wrapping difference
+ *     (sequence_number.rs:76-101).
+ *   `f32 as u32` is Rust's cast: NaN and negative values give 0, values >= 2^32 give 0xFFFFFFFF, otherwise truncation.
+ *   Every f32 operation is rounded once, in source order, none contracted; the constants fold in f32: BETA_CUBIC =
+ *     0.7f, C = 0.4f, `1. - BETA_CUBIC` = fl(1 - 0.7f), `1. + BETA_CUBIC` = fl(1 + 0.7f), `3.*(1.-bc)/(1.+bc)` =
+ *     fl(fl(3 fl(1 - bc)) / fl(1 + bc)). Division is IEEE, denormals are kept. powi(3) of d is fl(fl(d d) d).
+ *   Duration::as_secs_f32 of ns nanoseconds is (float)(ns / 10^9) + (float)(ns % 10^9) / 1e9f. t =
+ *     as_secs_f32(now_ns - ca_start_ns), the difference saturating at 0 (Instant::elapsed); rtt =
+ *     as_secs_f32(rto_ns(rto)).
+ *   rto_ns(double rto) is Duration::from_secs_f64 (the reference's toolchain, nightly-2024-09-25): the real value
+ *     rto * 10^9 rounded to nearest, ties to even, computed exactly from rto's mantissa by a 64 x 64 -> 128-bit
+ *     product, never as an f64 product. One helper serves the device and the host: dk_tcp_rto_ns below. A row whose
+ *     rto is not in [0, 1e9] seconds (NaN included) is the connection-level failure E_RTO: the reference would panic.
+ *   K's cube root (cubic.rs:200) is the correctly rounded f32 cube root. A stated deviation: the reference calls the
+ *     platform's cbrtf, which is only faithful (glibc 2.35's differs from correct rounding on about a tenth of
+ *     uniform inputs, always by one ulp), so there is no single reference bit pattern to match. The device takes the
+ *     f64 cube root, rounds it to f32 and, where the f64 value lies within 2^-46 of the midpoint m of two f32
+ *     values, decides by the sign of x - m^3 computed exactly (m^2 is exact in f64, m^3 = p + e by one fma).
+ *
+ * The congestion-control state of one connection, indexed by flow id. Device memory, 16-byte aligned, updated in
+ * place. mss is tx_conns[c].mss. A row with DK_TCP_CC_CUBIC clear is the algorithm None (congestion_control/none.rs):
+ * every call leaves the row and tx_conns[c].cwnd untouched; dk_tcp_timers' deadline still works for it.
+ * ------------------------------------------------------------------------------------------------------------- */
+#define DK_TCP_CC_CUBIC 1u            /* clear: the algorithm None                                                 */
+#define DK_TCP_CC_FAST_CONVERGENCE 2u /* Cubic::fast_convergence (cubic.rs:42)                                     */
+#define DK_TCP_CC_IN_RECOVERY 4u      /* in_fast_recovery                                                          */
+#define DK_TCP_CC_LAST_WAS_RTO 8u     /* last_congestion_was_rto                                                   */
+#define DK_TCP_CC_RETRANSMIT_NOW 16u  /* fast_retransmit_now                                                       */
+
+typedef struct dk_tcp_cc_conn {
+    uint32_t flags;         /* DK_TCP_CC_*                                                                         */
+    uint32_t cwnd;          /* Cubic::cwnd (cubic.rs:41); Cubic::new: 4 / 3 / 2 x mss (mss <= 1095 / <= 2190 / above) */
+    uint32_t ssthresh;      /* new(): 0xFFFFFFFF                                                                   */
+    uint32_t w_max;         /* new(): 0                                                                            */
+    uint32_t initial_cwnd;
+    uint32_t ltci;          /* limited_transmit_cwnd_increase                                                      */
+    uint32_t dup_acks;      /* duplicate_ack_count                                                                 */
+    uint32_t rpif;          /* retransmitted_packets_in_flight                                                     */
+    uint32_t recover;       /* new(): the initial send sequence number                                             */
+    uint32_t prev_ack;      /* prev_ack_seq_no; new(): the initial send sequence number                            */
+    uint64_t ca_start_ns;   /* ca_start                                                                            */
+    uint64_t last_send_ns;  /* last_send_time                                                                      */
+    uint64_t rtt_at_last_send_ns;  /* rtt_at_last_send; new(): 10^9                                                */
+} dk_tcp_cc_conn;           /* 64 bytes */
+
+/* Duration::from_secs_f64(rto).as_nanos() as above; 0 for an rto outside [0, 1e9] (E_RTO's condition). Pure host
+ * function: the same code the kernels run. */
+uint64_t dk_tcp_rto_ns(double rto);
+
+enum dk_tcp_cc_status {
+    DK_TCP_CC_OK = 0,
+    DK_TCP_CC_E_STATE = 1,    /* tx_conns[c].state != DK_TCP_ESTABLISHED                                          */
+    DK_TCP_CC_E_SND_NXT = 2,  /* rx_conns[c].send_next != tx_conns[c].snd_nxt (dk_tcp_cc_ack only)                */
+    DK_TCP_CC_E_MSS = 3,      /* a CUBIC row with mss == 0: the reference divides by it                           */
+    DK_TCP_CC_E_RTO = 4       /* rto outside [0, 1e9] seconds or NaN                                              */
+};
+
+/* dk_tcp_cc_ack: SlowStartCongestionAvoidance::on_ack_received (cubic.rs:307-328 with :113-246) for a whole batch.
+ * It follows the dk_tcp_rx_process call of the same ctx as dk_tcp_ack_emit does (that call's rx, n, nconns, `action`
+ * and rx_conns), with a turn counter of its own, and it must precede that batch's dk_tcp_ack_process: it reads
+ * snd_una and rto as that call has not yet moved them. A call after the batch's dk_tcp_ack_process, a second call, a
+ * call out of turn or one with another n / nconns returns EINVAL and writes nothing. Its order with dk_tcp_ack_emit
+ * is free, with identical results.
+ * One lane per connection walks the connection's segments in arrival order and visits those whose action is DELIVERED,
+ * STORED, STORE_DUP, NO_DATA, FIN or ACK_UNSENT (ctrlblk.rs:629 calls congestion control before the ack <= SND.NXT
+ * test of :633). With a running una that starts at tx_conns[c].snd_una, per visited segment:
+ *   1. on_ack_received(rto, una, snd_nxt, ack), literally. Its quirks are kept: an old ACK (ack - una >= 2^31) is
+ *      "new data" to CUBIC (bytes_acknowledged != 0); retransmitted_packets_in_flight decrements on every duplicate;
+ *      recovery starts at the third duplicate by `ack - 1 > recover` or by the "retransmitted packet dropped" heuristic
+ *      (cwnd > mss and ack - prev_ack <= 4 mss); ca_start = now_ns on a full acknowledgement.
+ *   2. una = ack if the action is not ACK_UNSENT and 0 < ack - una < 2^31: dk_tcp_ack_process's rule, its 2^31
+ *      deviation included.
+ * Then the row is written and tx_conns[c].cwnd = cwnd + limited_transmit_cwnd_increase (wrapping), the effective
+ * window dk_tcp_tx_segment expects.
+ * One deviation: rto is one value per call, ack_conns[c].rto as the call finds it, as now_ns is. The reference reads
+ * it per segment; the two agree whenever no earlier segment of the same connection in the batch took an RTT sample
+ * (rto moves only in RtoCalculator::add_sample, and only congestion avoidance reads it).
+ * Connection-level failures, the first that applies (the row and tx_conns[c].cwnd stay untouched, counts 0): E_STATE,
+ * E_SND_NXT, E_MSS, E_RTO. A None row reports OK with counts 0.
+ * Outputs (device): status, new_acks (visited segments with ack != una), dup_acks (ack == una): [nconns];
+ * cwnd_after (optional): [n], cwnd after each visited segment, 0 elsewhere.
+ * Returns 0, EINVAL (also: a null required pointer, tx_conns / ack_conns / cc not 16-byte aligned) or EIO. */
+typedef struct dk_tcp_cc_ack_out {
+    uint32_t* status;
+    uint32_t* new_acks;
+    uint32_t* dup_acks;
+    uint32_t* cwnd_after;
+} dk_tcp_cc_ack_out;
+
+int dk_tcp_cc_ack(dk_tcp_ctx* ctx, const dk_rx_results* rx, uint32_t n, const uint8_t* action,
+                  const dk_tcp_conn* rx_conns, dk_tcp_tx_conn* tx_conns, const dk_tcp_ack_conn* ack_conns,
+                  dk_tcp_cc_conn* cc, uint32_t nconns, uint64_t now_ns, const dk_tcp_cc_ack_out* out, void* stream);
+
+/* dk_tcp_timers: one turn of background_retransmitter's loop (sender.rs:325-364) and the acknowledger's deadline for
+ * every connection. Per connection c, after the checks E_STATE, E_MSS (a CUBIC row with mss == 0: on_rto divides by
+ * it) and E_RTO, the first that applies (the row untouched, rtx_fire[c] = 0):
+ *   fast_retransmit_now set (a CUBIC row): on_fast_retransmit clears it (cubic.rs:346-351), rtx_fire[c] =
+ *     DK_TCP_RTX_FAST;
+ *   else rtx_armed and now_ns >= rtx_base_ns + rto_ns(rto) (the timer fires at expiry <= now, runtime/timer.rs:215; the
+ *     sum saturates): on_rto(snd_una) (cubic.rs:248-278, :330-334; nothing for None), rtx_fire[c] = DK_TCP_RTX_TIMEOUT;
+ *   else rtx_fire[c] = 0.
+ * on_rto runs before the retransmission, as in the reference; the back-off and the re-arming stay in dk_tcp_retransmit,
+ * which follows on the same stream with rtx_fire as its fire[]. A CUBIC connection whose queue is empty still consumes
+ * its flag, as the reference's loop does; an armed timer over an empty queue (unreachable in the reference, see
+ * dk_tcp_retransmit's IDLE note) still runs on_rto and fires here, and dk_tcp_retransmit then reports IDLE for it
+ * and leaves it armed: the caller that builds such a row gets a TIMEOUT at every call.
+ * tx_conns[c].cwnd is refreshed to cwnd + limited_transmit_cwnd_increase for CUBIC rows without a failure.
+ * With dack and ack_fire: ack_fire[c] = dack[c].armed != 0 && now_ns >= dack[c].deadline_ns, dk_tcp_ack_timer's fire[],
+ * whatever the row's status; dack is only read. Both or neither are given.
+ * Outputs (device): status [nconns]; n_fast, n_timeout, n_ack: one word each, the connections set in rtx_fire /
+ * ack_fire, so that the host can skip the follow-up calls without reading an array (n_ack = 0 without ack_fire).
+ * A call on dk_tcp_tx_ctx, serialised as dk_tcp_retransmit is. ack_conns is only read. nconns == 0 is a valid call that
+ * writes the three words. Returns 0, EINVAL (a null required pointer, a misaligned table) or EIO. */
+typedef struct dk_tcp_timers_out {
+    uint32_t* status;
+    uint32_t* n_fast;
+    uint32_t* n_timeout;
+    uint32_t* n_ack;
+} dk_tcp_timers_out;
+
+int dk_tcp_timers(dk_tcp_tx_ctx* ctx, dk_tcp_tx_conn* tx_conns, const dk_tcp_ack_conn* ack_conns, dk_tcp_cc_conn* cc,
+                  const dk_tcp_dack_conn* dack, uint32_t nconns, uint64_t now_ns, uint8_t* rtx_fire, uint8_t* ack_fire,
+                  const dk_tcp_timers_out* out, void* stream);
+
+/* dk_tcp_cc_send: the two hooks of Sender::send_segment, around one dk_tcp_tx_segment call on the same stream.
+ * DK_TCP_CC_BEFORE_SEND, on_cwnd_check_before_send (cubic.rs:290-298), for every CUBIC row: if now_ns - last_send_ns
+ *   (saturating at 0) is strictly greater than rtt_at_last_send_ns, cwnd = min(initial_cwnd, cwnd) and
+ *   limited_transmit_cwnd_increase = 0; then tx_conns[c].cwnd = cwnd + limited_transmit_cwnd_increase. push, nbufs
+ *   and results are not used.
+ * DK_TCP_CC_AFTER_SEND, on_send (cubic.rs:300-305), takes the push list, nbufs and the dk_tcp_tx_results of the
+ *   dk_tcp_tx_segment call just made: for every CUBIC connection that got at least one frame, last_send_ns = now_ns,
+ *   rtt_at_last_send_ns = rto_ns(rto), and limited_transmit_cwnd_increase = saturating_sub(it, the sum over the
+ *   connection's frames j of (snd_nxt before frame j - snd_una)): on_send is given the bytes in flight, not the bytes
+ *   sent, and it is called before send_segment moves SND.NXT over the frame (sender.rs:177, ahead of :193), so the
+ *   first frame of an idle connection takes nothing off; a quirk kept. A chain of saturating subtractions of
+ *   non-negative terms is one saturating subtraction of their sum, so the lane stops once the increase is 0.
+ *   tx_conns[c].cwnd is refreshed for those connections. A call that reported NO_ROOM sent nothing and changes
+ *   nothing.
+ * As dk_tcp_tx_segment's section says, cwnd does not move between the frames of one segmentation call.
+ * status [nconns]: OK, E_STATE, E_RTO (AFTER_SEND only, for a connection that got frames; the row untouched).
+ * A call on dk_tcp_tx_ctx, serialised as dk_tcp_tx_segment is. Returns 0, EINVAL (a phase that is neither, a null
+ * required pointer, a misaligned table) or EIO. */
+enum dk_tcp_cc_phase { DK_TCP_CC_BEFORE_SEND = 0, DK_TCP_CC_AFTER_SEND = 1 };
+
+int dk_tcp_cc_send(dk_tcp_tx_ctx* ctx, uint32_t phase, dk_tcp_tx_conn* tx_conns, const dk_tcp_ack_conn* ack_conns,
+                   dk_tcp_cc_conn* cc, uint32_t nconns, const dk_tcp_tx_push* push, uint32_t nbufs,
+                   const dk_tcp_tx_results* results, uint64_t now_ns, uint32_t* status, void* stream);
 
 #ifdef __cplusplus
 }
