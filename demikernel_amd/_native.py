@@ -319,6 +319,23 @@ TCP_CC_FUNCTIONS = [
                                c_uint32, POINTER(DkTcpTxResults), c_uint64, c_void_p, c_void_p]),
 ]
 
+# include/dk_tcp.h, the send side's bookkeeping (dk_tcp_tx_commit, dk_tcp_rtx_piggyback)
+TCP_COMMIT_STATUSES = ["OK", "E_QUEUE", "E_FULL"]
+DK_TCP_COMMIT_OK, DK_TCP_COMMIT_E_QUEUE, DK_TCP_COMMIT_E_FULL = range(3)
+TCP_COMMIT_OUT_FIELDS = ["status", "appended"]
+
+
+class DkTcpCommitOut(ctypes.Structure):
+    _fields_ = [(name, c_void_p) for name in TCP_COMMIT_OUT_FIELDS]
+
+
+TCP_COMMIT_FUNCTIONS = [
+    ("dk_tcp_tx_commit", c_int, [c_void_p, POINTER(DkTcpTxPush), c_uint32, POINTER(DkTcpTxResults), c_uint32, c_void_p,
+                                 c_uint32, POINTER(DkTcpUnacked), c_uint32, c_uint32, c_void_p, c_uint64,
+                                 POINTER(DkTcpCommitOut), c_void_p]),
+    ("dk_tcp_rtx_piggyback", c_int, [c_void_p, POINTER(DkTcpRtxResults), c_void_p, c_uint32, c_void_p]),
+]
+
 # include/dk_diag.h (diagnostics, not the receive ABI)
 # include/dk_demi.h: delivered frames as demi_sgarray_t (host-side, no GPU work)
 class DemiSgaseg(ctypes.Structure):
@@ -373,6 +390,8 @@ DIAG_FUNCTIONS = [
     ("dk_diag_tcp_ack_emit_set_form", c_int, [c_void_p, c_int32]),
     ("dk_diag_tcp_ack_emit_last_form", c_int, [c_void_p]),
     ("dk_diag_tcp_cc_cbrt", c_int, [c_void_p, c_void_p, c_uint32, c_void_p]),
+    ("dk_diag_tcp_commit_set_form", c_int, [c_void_p, c_int32]),
+    ("dk_diag_tcp_commit_last_form", c_int, [c_void_p]),
 ]
 DK_DIAG_RX_KNOBS = ["stage", "split", "small", "sched", "grid", "grid_per_cu", "debug", "lds_table", "tail", "udp_table",
                     "host_zc"]
@@ -380,9 +399,10 @@ DK_TCP_WALKS = {"lane": 0, "wave": 1, "relay": 2, "scan": 3}
 DK_TCP_SORTS = {"counting": 0, "radix": 1}
 DK_TCP_ACK_FORMS = {"lane": 0, "wave": 1, "chip": 2}
 DK_TCP_ACK_EMIT_FORMS = {"lane": 0, "scan": 1}
+DK_TCP_COMMIT_FORMS = {"conn": 0, "chip": 1}
 
 ALL_FUNCTIONS = (FUNCTIONS + RING_FUNCTIONS + TCP_FUNCTIONS + TCP_ACK_FUNCTIONS + TCP_TX_FUNCTIONS + TCP_RTX_FUNCTIONS +
-                 TCP_ACKEMIT_FUNCTIONS + TCP_CC_FUNCTIONS + DIAG_FUNCTIONS +
+                 TCP_ACKEMIT_FUNCTIONS + TCP_CC_FUNCTIONS + TCP_COMMIT_FUNCTIONS + DIAG_FUNCTIONS +
                  DEMI_FUNCTIONS + COMM_FUNCTIONS)
 
 _lib = None

@@ -57,14 +57,29 @@ struct dk_tcp_order {
 // 0, or EINVAL for a null context.
 int dk_tcp_ctx_order(dk_tcp_ctx* ctx, dk_tcp_order* out);
 
+// dk_tcp_tx_commit's state in a dk_tcp_tx_ctx (tcp_commit_kernels.hip): its turn after a dk_tcp_tx_segment call, the
+// form override and the chip form's per-connection bases (device; freed by dk_tcp_tx_ctx_destroy).
+struct dk_tcp_commit_state {
+    int form = -1;           // dk_diag_tcp_commit_set_form: 0 conn, 1 chip, -1 the rule
+    int last_form = -1;      // the form the last dk_tcp_tx_commit call ran
+    uint32_t seg_call = 0;   // the dk_tcp_tx_segment calls of this context that returned 0
+    uint32_t seg_nbufs = 0;  // the last one's nbufs
+    uint32_t done = 0;       // the dk_tcp_tx_segment call number the last dk_tcp_tx_commit call consumed
+    void* scratch = nullptr;
+    size_t scratch_cap = 0;
+};
+
 // The serialisation state of a dk_tcp_tx_ctx (tcp_tx_kernels.hip), for the calls on it that live in other files
-// (dk_tcp_timers, dk_tcp_cc_send: tcp_cc_kernels.hip). They use no scratch of the context.
+// (dk_tcp_timers, dk_tcp_cc_send: tcp_cc_kernels.hip; dk_tcp_tx_commit, dk_tcp_rtx_piggyback: tcp_commit_kernels.hip).
+// Only dk_tcp_tx_commit uses scratch of the context, its own.
 struct dk_tcp_tx_ctx;
 struct dk_tcp_tx_serial {
     int device;
     hipEvent_t last;
     hipStream_t* last_stream;
     bool* used;
+    uint32_t cus;
+    dk_tcp_commit_state* commit;
 };
 
 // 0, or EINVAL for a null context.

@@ -426,11 +426,13 @@ struct dk_tcp_tx_ctx {
     // dk_tcp_ack_timer's emit flags / their scan per connection (tot[4] is its total)
     uint64_t* ackt_emit = nullptr;
     size_t ackt_emit_cap = 0;
+    // dk_tcp_tx_commit's turn after dk_tcp_tx_segment, its form and its scratch (tcp_commit_kernels.hip)
+    dk_tcp_commit_state commit;
 };
 
 int dk_tcp_tx_ctx_serial(dk_tcp_tx_ctx* t, dk_tcp_tx_serial* o) {
     if (!t || !o) return EINVAL;
-    *o = dk_tcp_tx_serial{t->device, t->last, &t->last_stream, &t->used};
+    *o = dk_tcp_tx_serial{t->device, t->last, &t->last_stream, &t->used, t->cus, &t->commit};
     return 0;
 }
 
@@ -479,7 +481,7 @@ void dk_tcp_tx_ctx_destroy(dk_tcp_tx_ctx* t) {
     if (t->used) (void)hipEventSynchronize(t->last);
     for (void* p : {(void*)t->seqsp, (void*)t->flags, (void*)t->frames, (void*)t->bsum, (void*)t->tot, (void*)t->head,
                     (void*)t->tail, (void*)t->rec, (void*)t->cm, (void*)t->rtx_emit, (void*)t->rtx_rec,
-                    (void*)t->ackt_emit})
+                    (void*)t->ackt_emit, t->commit.scratch})
         if (p) (void)hipFree(p);
     (void)hipEventDestroy(t->last);
     delete t;
@@ -544,6 +546,8 @@ int dk_tcp_tx_segment(dk_tcp_tx_ctx* t, const uint8_t* src, uint64_t src_bytes, 
     if (hipEventRecord(t->last, s) != hipSuccess) return EIO;
     t->last_stream = s;
     t->used = true;
+    if (++t->commit.seg_call == 0) t->commit.seg_call = 1;  // dk_tcp_tx_commit's turn; 0 stays "no call yet"
+    t->commit.seg_nbufs = nbufs;
     return 0;
 }
 

@@ -4,8 +4,8 @@ CUBIC as tcp/established/congestion_control/cubic.rs states it, for every connec
 on_ack_received over a batch (it follows TcpReceiver.process and precedes TcpAcker.process on the same batch), timers
 names the connections whose retransmit deadline or fast-retransmit flag fires (running on_rto / on_fast_retransmit) and
 whose delayed ACK is due, and cc_send is the pair of hooks around TcpSender.segment. With them a lossy transfer runs
-cc_send(before) -> segment -> cc_send(after) -> rx -> cc_ack -> ack_process -> ack_emit -> timers -> retransmit /
-ack_timer with the host advancing only its clock: it fills no fire[] and no cwnd.
+cc_send(before) -> segment -> tx_commit (tcp_commit.py) -> cc_send(after) -> rx -> cc_ack -> ack_process -> ack_emit
+-> timers -> retransmit / ack_timer with the host advancing only its clock: it fills no fire[] and no cwnd.
 """
 from __future__ import annotations
 

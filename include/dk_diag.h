@@ -92,6 +92,12 @@ int dk_diag_tcp_ack_emit_set_form(struct dk_tcp_ctx* ctx, int32_t form);
 /* The form the context's last dk_tcp_ack_emit call ran (0 lane, 1 scan; -1 none yet, or a call with no segments or no
  * table rows). */
 int dk_diag_tcp_ack_emit_last_form(const struct dk_tcp_ctx* ctx);
+/* Which form dk_tcp_tx_commit runs (dk_tcp.h): form -1 the engine's rule, 0 one wave per connection, 1 the chip form
+ * (one wave per connection for the decision and the move, one lane per frame for the entries). 0 or EINVAL. */
+struct dk_tcp_tx_ctx;
+int dk_diag_tcp_commit_set_form(struct dk_tcp_tx_ctx* ctx, int32_t form);
+/* The form the context's last dk_tcp_tx_commit call ran (0 conn, 1 chip; -1 none yet, or a call with no table rows). */
+int dk_diag_tcp_commit_last_form(const struct dk_tcp_tx_ctx* ctx);
 /* The device's correctly rounded f32 cube root (dk_tcp.h, congestion control: K), applied to in[0 .. n) into
  * out[0 .. n) (device arrays) on `stream`: what dk_tcp_cc_ack's lanes call. Returns 0, EINVAL or EIO. */
 int dk_diag_tcp_cc_cbrt(const float* in, float* out, uint32_t n, void* stream);

@@ -366,7 +366,7 @@ int dk_tcp_ack_process(dk_tcp_ctx* ctx, const dk_rx_results* rx, uint32_t n, con
  * Capacity is all or nothing, tested on the device exactly as dk_tcp_tx_segment tests it: n_frames always reports the
  * frames the call needs; if that exceeds max_frames, or n_frames * slot_stride exceeds out_bytes, no frame, no tx_time
  * and no ack_conns field is written, the connections that had a frame report NO_ROOM and every frame[c] is 0xFFFFFFFF.
- * Ordering against dk_tcp_ack_process and the queue append, which touch the same rows, is the caller's: they run on
+ * Ordering against dk_tcp_ack_process and dk_tcp_tx_commit, which touch the same rows, is the caller's: they run on
  * one stream. This entry point is additive: DK_RX_ABI_VERSION stays 4.
  * ------------------------------------------------------------------------------------------------------------- */
 enum dk_tcp_rtx_fire { DK_TCP_RTX_NONE = 0, DK_TCP_RTX_TIMEOUT = 1, DK_TCP_RTX_FAST = 2 };
@@ -452,8 +452,9 @@ int dk_tcp_retransmit(dk_tcp_tx_ctx* ctx, const uint8_t* src, uint64_t src_bytes
  * frames report NO_ROOM (n_acks still holds their need). Such a dk_tcp_ack_emit call has taken its turn all the same
  * (the test is made on the device): n slots are the most a batch can need. Nothing but dack, the frames and the
  * outputs is ever written.
- * Not modelled: clearing armed when a data frame of the connection piggybacks the ACK (emit, :761):
- * dk_tcp_tx_segment and dk_tcp_retransmit do not touch dack, which costs one redundant pure ACK per delay.
+ * Clearing armed when a data frame of the connection piggybacks the ACK (emit, :761) is not done by
+ * dk_tcp_tx_segment and dk_tcp_retransmit themselves, which do not touch dack: it is dk_tcp_tx_commit's and
+ * dk_tcp_rtx_piggyback's (below), the calls that follow them.
  * These entry points are additive: DK_RX_ABI_VERSION stays 4.
  * ------------------------------------------------------------------------------------------------------------- */
 /* The delayed-ACK state of one connection, indexed by flow id. Device memory, 16-byte aligned, updated in place. */
@@ -681,6 +682,70 @@ enum dk_tcp_cc_phase { DK_TCP_CC_BEFORE_SEND = 0, DK_TCP_CC_AFTER_SEND = 1 };
 int dk_tcp_cc_send(dk_tcp_tx_ctx* ctx, uint32_t phase, dk_tcp_tx_conn* tx_conns, const dk_tcp_ack_conn* ack_conns,
                    dk_tcp_cc_conn* cc, uint32_t nconns, const dk_tcp_tx_push* push, uint32_t nbufs,
                    const dk_tcp_tx_results* results, uint64_t now_ns, uint32_t* status, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * The send side's bookkeeping: the "post-send operations" of Sender::send_segment (sender.rs:195-206) and of
+ * ControlBlock::emit (ctrlblk.rs:761), for every connection of one dk_tcp_tx_segment call at once. Every frame that
+ * call sent is pushed onto its connection's unacknowledged queue with its transmit time, a disarmed retransmit timer
+ * is armed, and the delayed-ACK deadline of a connection that sent anything is cancelled: the frames carried the ACK.
+ * Regions: connection c owns pool[c * q_cap, (c + 1) * q_cap); its live entries pool[q_first, q_first + q_count) lie
+ * inside it.
+ * Which frames: the frames of buffer b count iff results->status[b] is DK_TCP_TX_SENT or DK_TCP_TX_PARTIAL; they are
+ * first_frame[b] .. first_frame[b] + frame_count[b]), and a connection's frames are consecutive. k = their number for
+ * the connection. Nothing is read by the host: n_frames stays on the device.
+ * Per connection c with k > 0, the first of these that applies (64-bit arithmetic):
+ *   E_QUEUE  q_count > q_cap, or q_count > 0 and [q_first, q_first + q_count) is not inside the region
+ *   E_FULL   q_count + k > q_cap. A sizing error of the caller's: the frames are already on the wire and cannot be
+ *            queued later, so they will never be retransmitted. Size q_cap for the largest window in segments
+ *            (dk_tcp_tx_segment is not limited by queue room).
+ *   both leave the row and the region untouched, appended = 0.
+ *   q_count == 0: q_first' = c * q_cap, whatever q_first was;
+ *   q_first + q_count + k <= (c + 1) * q_cap: the entries go in place, q_first' = q_first;
+ *   otherwise the live entries move, in order, to the start of the region and q_first' = c * q_cap.
+ * Entry j of the connection, for frame f of buffer b, is pool[q_first' + q_count + j] = {off = push->off[b] + the
+ * payload bytes of b's earlier frames (wrapping), len = len_out[f] - 54 (the FIN frame becomes the end-of-send marker,
+ * len 0), tx_time = now_ns}. Then q_count' = q_count + k, and if rtx_armed == 0: rtx_armed = 1, rtx_base_ns = now_ns
+ * (a nonzero rtx_armed is armed and keeps its base). No other field of the row is written. Entries of the region
+ * outside the new live range hold unspecified values after a successful commit.
+ * With dack: dack[c].armed = 0 for every connection with k > 0, whatever its status; deadline_ns is left as it is
+ * (dk_tcp_ack_emit's rule); every other dack row keeps its bytes.
+ * Never written: the rows of connections with k == 0 (malformed ones too: their status is OK), other connections'
+ * regions, pool entries at or beyond nconns * q_cap, tx_conns, push, results.
+ * Turn: the call follows one dk_tcp_tx_segment call of the same ctx that returned 0, with that call's push, nbufs,
+ * results (frame_buf is required) and max_frames; dk_tcp_cc_send, dk_tcp_retransmit, dk_tcp_timers and dk_tcp_ack_timer
+ * may come between. Its order with dk_tcp_cc_send(AFTER_SEND) is free, with identical results. A second commit for
+ * one segmentation call, a commit with none before it or with another nbufs returns EINVAL and writes nothing. A
+ * segmentation call that reported NO_ROOM sent nothing: its commit is a valid call that changes nothing and writes
+ * status OK, appended 0 everywhere.
+ * The engine runs one wave per connection; at >= 1,024 frame slots (max_frames) per connection the chip form (one
+ * wave per connection for the decision, the move and the row, then one lane per frame across the chip for the
+ * entries); dk_diag_tcp_commit_set_form (dk_diag.h) forces a form. Results are identical. The environment is never
+ * read.
+ * Asynchronous on `stream`, serialised with the context's other calls as they are. nbufs == 0 and nconns == 0 are
+ * valid. Returns 0, EIO, ENOMEM or EINVAL (decided before any GPU work: a null required pointer, ack_conns / dack not
+ * 16-byte aligned, nconns * q_cap > nq, now_ns == DK_TCP_TX_TIME_NONE, which would read as "retransmitted", a call out
+ * of turn). This entry point is additive: DK_RX_ABI_VERSION stays 4.
+ * ------------------------------------------------------------------------------------------------------------- */
+enum dk_tcp_commit_status { DK_TCP_COMMIT_OK = 0, DK_TCP_COMMIT_E_QUEUE = 1, DK_TCP_COMMIT_E_FULL = 2 };
+
+/* Outputs (device), [nconns] each. */
+typedef struct dk_tcp_commit_out {
+    uint32_t* status;    /* enum dk_tcp_commit_status                 */
+    uint32_t* appended;  /* entries appended (0 on a failure)         */
+} dk_tcp_commit_out;
+
+int dk_tcp_tx_commit(dk_tcp_tx_ctx* ctx, const dk_tcp_tx_push* push, uint32_t nbufs,
+                     const dk_tcp_tx_results* results, uint32_t max_frames, dk_tcp_ack_conn* ack_conns,
+                     uint32_t nconns, const dk_tcp_unacked* q, uint32_t nq, uint32_t q_cap,
+                     dk_tcp_dack_conn* dack /* optional */, uint64_t now_ns, const dk_tcp_commit_out* out,
+                     void* stream);
+
+/* A retransmitted frame carries the ACK too: dack[c].armed = 0 where results->status[c] == DK_TCP_RTX_SENT, for the
+ * results of any dk_tcp_retransmit call; every other byte is untouched. Idempotent; it takes no turn. A call on
+ * dk_tcp_tx_ctx, serialised as dk_tcp_retransmit is. Returns 0, EINVAL (a null required pointer, a misaligned dack)
+ * or EIO. */
+int dk_tcp_rtx_piggyback(dk_tcp_tx_ctx* ctx, const dk_tcp_rtx_results* results, dk_tcp_dack_conn* dack,
+                         uint32_t nconns, void* stream);
 
 #ifdef __cplusplus
 }
