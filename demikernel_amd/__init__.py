@@ -27,7 +27,9 @@ from .tcp_rtx import RtxResults, retransmit, retransmit_batch  # noqa: F401
 from .tcp_ackemit import AckEmitResults, ack_emit, ack_emit_batch, ack_timer, dack_conn_table  # noqa: F401
 from .tcp_cc import CcAckOut, TimersOut, cc_ack, cc_conn_table, cc_send, timers  # noqa: F401
 from .tcp_commit import CommitOut, rtx_piggyback, tx_commit  # noqa: F401
+from .tcp_listen import ListenResults, ListenTable, listen_process, listen_release, listen_timers, listener_table  # noqa: F401
 
-__all__ = ["CommitOut", "rtx_piggyback", "tx_commit", "CcAckOut", "TimersOut", "cc_ack", "cc_conn_table", "cc_send", "timers", "AckEmitResults", "ack_emit", "ack_emit_batch", "ack_timer", "dack_conn_table", "RtxResults", "retransmit", "retransmit_batch", "TcpAcker", "TcpAckOut", "UnackedQueue", "ack_conn_table", "sync_send_next", "PushList", "TcpSender", "TcpTxResults", "tx_conn_table","Comm", "Config", "Fail", "FrameBatch", "RxEngine", "RxResults", "SocketId", "V", "VERDICTS", "flow_array",
+__all__ = ["ListenResults", "ListenTable", "listen_process", "listen_release", "listen_timers", "listener_table",
+           "CommitOut", "rtx_piggyback", "tx_commit", "CcAckOut", "TimersOut", "cc_ack", "cc_conn_table", "cc_send", "timers", "AckEmitResults", "ack_emit", "ack_emit_batch", "ack_timer", "dack_conn_table", "RtxResults", "retransmit", "retransmit_batch", "TcpAcker", "TcpAckOut", "UnackedQueue", "ack_conn_table", "sync_send_next", "PushList", "TcpSender", "TcpTxResults", "tx_conn_table","Comm", "Config", "Fail", "FrameBatch", "RxEngine", "RxResults", "SocketId", "V", "VERDICTS", "flow_array",
            "ipv4", "ipv4_str", "raise_for_verdict", "tx_tuning", "TxSegments", "tx_header_bytes", "tx_links",
            "tx_serialize"]

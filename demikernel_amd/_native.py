@@ -336,6 +336,78 @@ TCP_COMMIT_FUNCTIONS = [
     ("dk_tcp_rtx_piggyback", c_int, [c_void_p, POINTER(DkTcpRtxResults), c_void_p, c_uint32, c_void_p]),
 ]
 
+# include/dk_tcp.h, the passive open (dk_tcp_listen_*)
+DK_TCP_LSN_NONE = 0xFFFFFFFF
+DK_TCP_LSN_NO_WSCALE = 0xFF
+DK_TCP_LSN_FALLBACK_MSS = 536
+DK_TCP_LSN_MAX_LISTENERS = 65535
+DK_TCP_LSN_SYNACK_BYTES, DK_TCP_LSN_RST_BYTES = 62, 54
+DK_TCP_LSN_KEY_FREE = 0xFFFFFFFFFFFFFFFF
+DK_TCP_LSN_KEY_TOMBSTONE = 0xFFFF << 48
+DK_TCP_LSN_CLOSED, DK_TCP_LSN_LISTENING = 0, 1
+TCP_LSN_SLOT_STATES = ["FREE", "SYN_RCVD", "ESTAB", "FAILED", "TOMBSTONE"]
+TCP_LSN_ACTIONS = ["SKIP", "SYN_ACCEPTED", "ESTABLISHED", "ESTABLISHED_DATA", "BAD_ACK", "FORWARD", "ORPHANED",
+                   "RST_FLAGS", "RST_BACKLOG"]
+TCP_LSN_STATUSES = ["OK", "E_WSCALE", "E_LINK", "E_SLOT", "E_TABLE", "NO_ROOM"]
+LISTENER_DTYPE = np.dtype([("state", "<u4"), ("flow_id", "<u4"), ("local_ip", "<u4"), ("local_port", "<u2"),
+                           ("receive_window_size", "<u2"), ("max_backlog", "<u4"), ("nonce", "<u4"),
+                           ("advertised_mss", "<u2"), ("window_scale", "u1"), ("reserved0", "u1"),
+                           ("handshake_retries", "<u4"), ("handshake_timeout_ns", "<u8"), ("ip_word", "<u4"),
+                           ("link", "<u4"), ("inflight", "<u4"), ("isn_counter", "<u2"), ("reserved1", "<u2"),
+                           ("reserved2", "<u8")])
+LSN_SLOT_DTYPE = np.dtype([("key", "<u8"), ("state", "<u4"), ("err", "<u4"), ("remote_isn", "<u4"),
+                           ("local_isn", "<u4"), ("syn_window", "<u2"), ("mss", "<u2"), ("remote_wscale", "u1"),
+                           ("reserved0", "u1"), ("reserved1", "<u2"), ("retries_left", "<u4"), ("reserved2", "<u4"),
+                           ("deadline_ns", "<u8")])
+LSN_READY_DTYPE = np.dtype([("listener", "<u4"), ("remote_ip", "<u4"), ("remote_port", "<u2"), ("err", "<u2"),
+                            ("frame", "<u4"), ("rcv_nxt", "<u4"), ("snd_nxt", "<u4"), ("local_window", "<u4"),
+                            ("remote_window", "<u4"), ("mss", "<u4"), ("local_wscale", "u1"), ("remote_wscale", "u1"),
+                            ("reserved0", "<u2"), ("slot", "<u4"), ("reserved1", "<u4")])
+assert LISTENER_DTYPE.itemsize == 64 and LSN_SLOT_DTYPE.itemsize == 48 and LSN_READY_DTYPE.itemsize == 48
+TCP_LSN_RESULT_FIELDS = ["action", "slot", "reply_frame", "off_out", "len_out", "frame_seg", "ready", "status",
+                         "n_frames", "n_ready"]
+_NP_C = {"<u4": c_uint32, "<u2": c_uint16, "u1": c_uint8, "|u1": c_uint8, "<u8": c_uint64}
+
+
+def _mirror(dtype: np.dtype):
+    return [(k, _NP_C[dtype.fields[k][0].str]) for k in dtype.names]
+
+
+class DkTcpListener(ctypes.Structure):
+    _fields_ = _mirror(LISTENER_DTYPE)
+
+
+class DkTcpLsnSlot(ctypes.Structure):
+    _fields_ = _mirror(LSN_SLOT_DTYPE)
+
+
+class DkTcpLsnReady(ctypes.Structure):
+    _fields_ = _mirror(LSN_READY_DTYPE)
+
+
+class DkTcpLsnResults(ctypes.Structure):
+    _fields_ = [(name, c_void_p) for name in TCP_LSN_RESULT_FIELDS]
+
+
+TCP_LISTEN_FUNCTIONS = [
+    ("dk_tcp_listen_table_create", c_int, [c_int32, c_uint32, POINTER(c_void_p)]),
+    ("dk_tcp_listen_table_destroy", None, [c_void_p]),
+    ("dk_tcp_listen_table_stats", c_int, [c_void_p, POINTER(c_uint32), POINTER(c_uint64)]),
+    ("dk_tcp_listen_table_read", c_int, [c_void_p, c_void_p]),
+    ("dk_tcp_listen_table_write", c_int, [c_void_p, c_void_p]),
+    ("dk_tcp_listen_key", c_uint64, [c_uint32, c_uint32, c_uint16]),
+    ("dk_tcp_listen_home", c_uint32, [c_uint32, c_uint64]),
+    ("dk_tcp_listen_backlog_fits", c_int, [c_uint32, c_uint64]),
+    ("dk_tcp_listen_process", c_int, [c_void_p, POINTER(DkRxResults), c_uint32, c_void_p, c_uint32, c_uint64, c_void_p,
+                                      c_uint32, c_void_p, c_void_p, c_uint32, c_uint64, c_void_p, c_uint64,
+                                      POINTER(DkTcpTxLayout), c_uint32, c_uint32, c_uint32, POINTER(DkTcpLsnResults),
+                                      c_void_p]),
+    ("dk_tcp_listen_timers", c_int, [c_void_p, c_void_p, c_uint32, c_uint64, c_void_p, c_uint32, c_uint64, c_void_p,
+                                     c_uint64, POINTER(DkTcpTxLayout), c_uint32, c_uint32, c_uint32,
+                                     POINTER(DkTcpLsnResults), c_void_p]),
+    ("dk_tcp_listen_release", c_int, [c_void_p, c_void_p, c_uint32, c_void_p, c_uint32, c_void_p, c_void_p]),
+]
+
 # include/dk_diag.h (diagnostics, not the receive ABI)
 # include/dk_demi.h: delivered frames as demi_sgarray_t (host-side, no GPU work)
 class DemiSgaseg(ctypes.Structure):
@@ -402,7 +474,8 @@ DK_TCP_ACK_EMIT_FORMS = {"lane": 0, "scan": 1}
 DK_TCP_COMMIT_FORMS = {"conn": 0, "chip": 1}
 
 ALL_FUNCTIONS = (FUNCTIONS + RING_FUNCTIONS + TCP_FUNCTIONS + TCP_ACK_FUNCTIONS + TCP_TX_FUNCTIONS + TCP_RTX_FUNCTIONS +
-                 TCP_ACKEMIT_FUNCTIONS + TCP_CC_FUNCTIONS + TCP_COMMIT_FUNCTIONS + DIAG_FUNCTIONS +
+                 TCP_ACKEMIT_FUNCTIONS + TCP_CC_FUNCTIONS + TCP_COMMIT_FUNCTIONS + TCP_LISTEN_FUNCTIONS +
+                 DIAG_FUNCTIONS +
                  DEMI_FUNCTIONS + COMM_FUNCTIONS)
 
 _lib = None

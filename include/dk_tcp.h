@@ -23,7 +23,9 @@
  * Congestion control (CUBIC's on_ack_received, on_rto, on_fast_retransmit and its two send hooks) and deciding which
  * timers have expired are dk_tcp_cc_ack, dk_tcp_timers and dk_tcp_cc_send, the last section: where the sections
  * between say that cwnd is an input or that the host fills fire[], those calls are what computes them on the device.
- * Not modelled: states other than ESTABLISHED (FIN-WAIT-1/2 etc.), the persist timer, repacketization.
+ * Creating a connection (the passive open: SYN, SYN+ACK, the handshake ACK and its timeout, the backlog) is the
+ * dk_tcp_listen_* section at the end.
+ * Not modelled: the active open, the closing states (FIN-WAIT-1/2, LAST-ACK etc.), the persist timer, repacketization.
  *
  * Conventions as dk_rx.h: 0 or a positive errno; device pointers; asynchronous on the caller's stream. A context holds
  * one set of scratch buffers: calls on one context are serialised — a call on another stream than the previous call
@@ -746,6 +748,248 @@ int dk_tcp_tx_commit(dk_tcp_tx_ctx* ctx, const dk_tcp_tx_push* push, uint32_t nb
  * or EIO. */
 int dk_tcp_rtx_piggyback(dk_tcp_tx_ctx* ctx, const dk_tcp_rtx_results* results, dk_tcp_dack_conn* dack,
                          uint32_t nconns, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * The passive open: what SharedPassiveSocket does with the frames that reach a listening socket (passive_open.rs:
+ * poll :137-195, handle_new_syn :197-240, send_rst :243-285, send_syn_ack_and_wait_for_ack :287-359, send_syn_ack
+ * :361-393, wait_for_ack :395-481), for every listener-bound frame of one dk_rx_process batch at once. The
+ * `connections` maps of all listeners are one open-addressing table in device memory that the device itself inserts
+ * into (dk_tcp_listen_table); the listeners are rows of dk_tcp_listener; lsn_of_flow[nflows] maps a frame's flow_id (a
+ * DK_FLOW_TCP_PASSIVE entry of the socket table) to its listener row, DK_TCP_LSN_NONE for every other flow.
+ *
+ * dk_tcp_listen_process covers the frames with verdict DK_V_OK_TCP whose flow_id maps to a listener that is
+ * LISTENING and passes the listener checks below; every other frame gets action SKIP. Frames are taken in arrival
+ * order (batch index), and each coroutine is taken to have run to its next await before the next frame arrives (the
+ * reference's scheduler leaves that open). The key is (listener row, remote ip, remote port). Per frame:
+ *   1. The key has an entry.
+ *      SYN_RCVD     the segment wait_for_ack pops. ack_num != local_isn + 1: the entry becomes FAILED / EBADMSG, action
+ *                   BAD_ACK, an error record goes to the ready list. Otherwise the entry becomes ESTABLISHED, action
+ *                   ESTABLISHED, or ESTABLISHED_DATA when the payload is not empty (the reference re-queues the segment
+ *                   for the new socket), and a ready record is appended. Nothing else is tested, as in the reference:
+ *                   not the ACK bit, RST, SYN or seq. A retransmitted SYN therefore fails the handshake.
+ *      ESTABLISHED  action FORWARD: the frame is for the socket's ControlBlock::poll; the host routes it by slot[].
+ *      FAILED       action ORPHANED. The reference never removes the entry of a failed handshake: it stays, swallows
+ *                   the remote's frames and counts against the backlog until dk_tcp_listen_release. The quirk is kept.
+ *   2. No entry.
+ *      !syn || ack || rst: a RST reply, action RST_FLAGS.
+ *      Otherwise a SYN (its payload is ignored). inflight >= max_backlog: a RST reply, action RST_BACKLOG. Otherwise
+ *      an entry is made: local_isn = crc + isn_counter (wrapping u32), then isn_counter += 1 (wrapping u16);
+ *      remote_isn = seq; syn_window = the raw header window; mss = the SYN's last MaximumSegmentSize entry, else
+ *      DK_TCP_LSN_FALLBACK_MSS; remote_wscale = its last WindowScale entry, else DK_TCP_LSN_NO_WSCALE; retries_left =
+ *      handshake_retries; deadline_ns = now_ns + handshake_timeout_ns; inflight += 1. A SYN+ACK reply, action
+ *      SYN_ACCEPTED.
+ * crc (isn_generator.rs:28-42, the non-test build) is CRC-32/CKSUM (polynomial 0x04C11DB7, initial value 0, not
+ * reflected, final XOR 0xFFFFFFFF; check value 0x765E7680) over 16 bytes: the remote ip's octets, the remote port
+ * big-endian, the local ip's octets, the local port big-endian, the nonce big-endian.
+ *
+ * Replies are the bytes dk_tx_serialize writes for the same descriptor with an empty payload; DK_TX_OFFLOAD_TCP in
+ * `flags` writes the TCP checksum as 0 (the reference passes its *rx* checksum-offload setting to
+ * serialize_and_attach here, :278 and :388; the caller decides what to pass). Addresses and ports are the frame's,
+ * swapped (source = the listener's local_ip / local_port); ip_word is the listener's; the link is link[i] when a
+ * per-frame link[] is given and link[i] < nlinks, else the listener's.
+ *   SYN+ACK  62 bytes: flags SYN|ACK, seq = local_isn, ack = remote_isn + 1, window = receive_window_size unscaled,
+ *            options [MSS(advertised_mss), WindowScale(window_scale)] (a 28-byte TCP header).
+ *   RST      54 bytes: flags RST|ACK, window 0. The frame had ACK: seq = its ack_num, ack = ack_num + 1. Otherwise
+ *            seq = 0, ack = seq_num + compute_size(), where compute_size() (header.rs:408-421) is taken over the
+ *            *parsed* option list: dk_tx_header_bytes(6, opts) - 34, not the received data offset.
+ * Replies are numbered in the order of the frames that triggered them; reply f owns slot f under dk_tcp_tx_layout's
+ * rule; no byte of out outside the frames is written.
+ * The ready list holds one record per ESTABLISHED / ESTABLISHED_DATA / BAD_ACK frame, in the order of those frames
+ * (the accept queue's order), with every argument EstablishedSocket::new receives at :457-478: see dk_tcp_lsn_ready.
+ *
+ * Listener checks, the first that applies (status[l]; the listener's frames are SKIP, nothing of it changes):
+ *   E_WSCALE  window_scale > 14 (the reference would panic on the shift)
+ *   E_LINK    link >= nlinks
+ *   E_SLOT    frame_lead + 62 > slot_stride
+ *   E_TABLE   2 x the sum of max_backlog over all rows exceeds the table's cap (every listener reports it, nothing is
+ *             done): with the rule kept an insert can never find the table full. The host states the sum as
+ *             backlog_sum (EINVAL when it breaks the rule); the device adds the rows up all the same.
+ * A CLOSED listener reports OK and its frames are SKIP.
+ * Capacity is all or nothing and tested on the device: n_frames and n_ready always report the call's need; if
+ * n_frames > max_frames, or n_frames * slot_stride > out_bytes, or n_ready > max_ready, then nothing else is written
+ * (no frame, ready record, per-frame result, table field or listener field) and the listeners that had a frame of
+ * theirs in the batch report NO_ROOM. There is no host round trip anywhere in the call.
+ * The slot a key lands in is not specified (concurrent inserts may win in either order); everything else is.
+ *
+ * dk_tcp_listen_timers is the handshake timeout (:316-357): every SYN_RCVD slot of a LISTENING listener that passes
+ * the checks with deadline_ns <= now_ns either has retries_left > 0: retries_left -= 1, deadline_ns = now_ns +
+ * handshake_timeout_ns and the same SYN+ACK goes out again from the slot's fields; or becomes FAILED / ETIMEDOUT with
+ * an error ready record (frame = DK_TCP_LSN_NONE). Same builder, same capacity rule. Its frames and records follow
+ * slot order, which is unspecified. Per-frame results (action, slot, reply_frame) are not used; frame_seg holds the slot.
+ * dk_tcp_listen_release is the socket_queue removal (:144-150): each key present becomes a TOMBSTONE, its listener's
+ * inflight goes down by one and found[k] = 1; an absent key gets found[k] = 0 (of two equal keys in one call exactly
+ * one is found; which one is not specified). A later
+ * insert may claim a tombstone; a lookup walks on across one. Tombstones lengthen walks over time: the count of
+ * never-used slots consumed is dk_tcp_listen_table_stats'. Rebuilding a worn table is out of scope.
+ *
+ * Calls on one table are serialised as a context's calls are; asynchronous on the caller's stream; the environment is
+ * never read. These entry points are additive: DK_RX_ABI_VERSION stays 4.
+ * Out of scope: turning a ready record into rows of the five TCP tables and an Active socket-table entry on the device
+ * (that needs a link and a queue region, which are the host's to give); feeding FORWARD frames to dk_tcp_rx_process
+ * before that entry exists; the active open; FIN-WAIT / LAST-ACK; SYN cookies (the reference has none).
+ * ------------------------------------------------------------------------------------------------------------- */
+#define DK_TCP_LSN_NONE 0xFFFFFFFFu
+#define DK_TCP_LSN_NO_WSCALE 0xFFu
+#define DK_TCP_LSN_FALLBACK_MSS 536u         /* FALLBACK_MSS (tcp/constants.rs)                                     */
+#define DK_TCP_LSN_MAX_LISTENERS 65535u      /* listener rows 0 .. 65,534: the row is 16 bits of the key            */
+#define DK_TCP_LSN_SYNACK_BYTES 62u
+#define DK_TCP_LSN_RST_BYTES 54u
+#define DK_TCP_LSN_KEY_FREE (~0ull)          /* the key word of a never-used slot                                   */
+#define DK_TCP_LSN_KEY_TOMBSTONE (0xFFFFull << 48)
+
+enum dk_tcp_lsn_listener_state { DK_TCP_LSN_CLOSED = 0, DK_TCP_LSN_LISTENING = 1 };
+
+/* One listening socket. Device memory, 16-byte aligned, updated in place (inflight, isn_counter). */
+typedef struct dk_tcp_listener {
+    uint32_t state;                /* enum dk_tcp_lsn_listener_state                                               */
+    uint32_t flow_id;              /* its index in the socket table (informational: lsn_of_flow is what is used)   */
+    uint32_t local_ip;             /* octet order, as dk_rx.h                                                      */
+    uint16_t local_port;
+    uint16_t receive_window_size;  /* TcpConfig::get_receive_window_size                                           */
+    uint32_t max_backlog;
+    uint32_t nonce;                /* IsnGenerator::nonce                                                          */
+    uint16_t advertised_mss;
+    uint8_t window_scale;          /* TcpConfig::get_window_scale                                                  */
+    uint8_t reserved0;
+    uint32_t handshake_retries;
+    uint64_t handshake_timeout_ns;
+    uint32_t ip_word;              /* dk_tx_segs.ip_word of the replies                                            */
+    uint32_t link;                 /* index into links[]                                                           */
+    uint32_t inflight;             /* connections.len(): moved by process (up) and release (down)                  */
+    uint16_t isn_counter;          /* IsnGenerator::counter                                                        */
+    uint16_t reserved1;
+    uint64_t reserved2;
+} dk_tcp_listener;                 /* 64 bytes */
+
+enum dk_tcp_lsn_slot_state {
+    DK_TCP_LSN_FREE = 0,       /* never used: a lookup stops here                                                  */
+    DK_TCP_LSN_SYN_RCVD = 1,
+    DK_TCP_LSN_ESTAB = 2,
+    DK_TCP_LSN_FAILED = 3,     /* err = EBADMSG or ETIMEDOUT                                                       */
+    DK_TCP_LSN_TOMBSTONE = 4   /* released: a lookup walks on, an insert may claim it                              */
+};
+
+/* One slot of the table, as dk_tcp_listen_table_read / _write move it. key = listener row << 48 | remote_ip << 16 |
+ * remote_port (dk_tcp_listen_key); DK_TCP_LSN_KEY_FREE / _TOMBSTONE for slots in those states, whose other fields
+ * are zero. */
+typedef struct dk_tcp_lsn_slot {
+    uint64_t key;
+    uint32_t state;          /* enum dk_tcp_lsn_slot_state                                                         */
+    uint32_t err;
+    uint32_t remote_isn;
+    uint32_t local_isn;
+    uint16_t syn_window;     /* the SYN's raw header window                                                        */
+    uint16_t mss;
+    uint8_t remote_wscale;   /* DK_TCP_LSN_NO_WSCALE: the SYN carried none                                         */
+    uint8_t reserved0;
+    uint16_t reserved1;
+    uint32_t retries_left;
+    uint32_t reserved2;
+    uint64_t deadline_ns;
+} dk_tcp_lsn_slot;           /* 48 bytes */
+
+enum dk_tcp_lsn_action {
+    DK_TCP_LSN_SKIP = 0,
+    DK_TCP_LSN_SYN_ACCEPTED = 1,
+    DK_TCP_LSN_ESTABLISHED = 2,
+    DK_TCP_LSN_ESTABLISHED_DATA = 3,
+    DK_TCP_LSN_BAD_ACK = 4,
+    DK_TCP_LSN_FORWARD = 5,
+    DK_TCP_LSN_ORPHANED = 6,
+    DK_TCP_LSN_RST_FLAGS = 7,
+    DK_TCP_LSN_RST_BACKLOG = 8
+};
+
+/* A ready-list record: what EstablishedSocket::new gets (:457-478), or the error ready.push(Err(..)) carries. The
+ * derived fields are computed for error records too. */
+typedef struct dk_tcp_lsn_ready {
+    uint32_t listener;
+    uint32_t remote_ip;
+    uint16_t remote_port;
+    uint16_t err;            /* 0, EBADMSG or ETIMEDOUT                                                            */
+    uint32_t frame;          /* the triggering batch frame; DK_TCP_LSN_NONE from dk_tcp_listen_timers              */
+    uint32_t rcv_nxt;        /* remote_isn + 1                                                                     */
+    uint32_t snd_nxt;        /* local_isn + 1                                                                      */
+    uint32_t local_window;   /* receive_window_size << local_wscale                                                */
+    uint32_t remote_window;  /* syn_window << remote_wscale                                                        */
+    uint32_t mss;
+    uint8_t local_wscale;    /* the listener's window_scale when the SYN carried a WindowScale option, else 0      */
+    uint8_t remote_wscale;   /* the option's value when below 14, else 14; 0 when the SYN carried none             */
+    uint16_t reserved0;
+    uint32_t slot;           /* the entry's slot: an opaque handle (slot[] of FORWARD frames names the same one)   */
+    uint32_t reserved1;
+} dk_tcp_lsn_ready;          /* 48 bytes */
+
+enum dk_tcp_lsn_status {
+    DK_TCP_LSN_OK = 0,
+    DK_TCP_LSN_E_WSCALE = 1,
+    DK_TCP_LSN_E_LINK = 2,
+    DK_TCP_LSN_E_SLOT = 3,
+    DK_TCP_LSN_E_TABLE = 4,
+    DK_TCP_LSN_NO_ROOM = 5
+};
+
+/* Outputs (device). Per batch frame, [n] (dk_tcp_listen_process only): action (enum dk_tcp_lsn_action), slot (the
+ * entry's slot for every action but SKIP, RST_FLAGS and RST_BACKLOG, else DK_TCP_LSN_NONE), reply_frame (its reply's
+ * frame index or DK_TCP_LSN_NONE). Per reply, [max_frames]: off_out, len_out (a dk_rx_batch over `out`), frame_seg
+ * (optional: the batch frame that triggered it; dk_tcp_listen_timers: the slot). ready: [max_ready]. status: [nl], enum
+ * dk_tcp_lsn_status. n_frames, n_ready: one word each, the call's need. */
+typedef struct dk_tcp_lsn_results {
+    uint8_t* action;
+    uint32_t* slot;
+    uint32_t* reply_frame;
+    uint32_t* off_out;
+    uint16_t* len_out;
+    uint32_t* frame_seg;
+    dk_tcp_lsn_ready* ready;
+    uint32_t* status;
+    uint32_t* n_frames;
+    uint32_t* n_ready;
+} dk_tcp_lsn_results;
+
+typedef struct dk_tcp_listen_table dk_tcp_listen_table;
+
+/* The table of `cap` slots (a power of two, at least 2) on `device`, all FREE, with the scratch of the calls on it.
+ * Returns 0, EINVAL (null out, cap not a power of two or below 2) or ENOMEM. */
+int dk_tcp_listen_table_create(int32_t device, uint32_t cap, dk_tcp_listen_table** out);
+void dk_tcp_listen_table_destroy(dk_tcp_listen_table* t);
+/* cap and the never-used slots consumed so far (either pointer may be null). Synchronous: waits for the table's calls.
+ * Returns 0, EINVAL or EIO. */
+int dk_tcp_listen_table_stats(dk_tcp_listen_table* t, uint32_t* cap, uint64_t* consumed);
+/* Copy the slots out to / in from rows[cap] (host memory). Synchronous: waits for the table's calls. _write recounts
+ * the consumed slots (those whose state is not FREE); the rows' placement is the caller's responsibility (a key must
+ * be reachable from its home slot across non-FREE slots). Returns 0, EINVAL or EIO. */
+int dk_tcp_listen_table_read(dk_tcp_listen_table* t, dk_tcp_lsn_slot* rows);
+int dk_tcp_listen_table_write(dk_tcp_listen_table* t, const dk_tcp_lsn_slot* rows);
+
+/* Pure host functions. The key word of (listener row, remote ip in octet order, remote port); the slot a key's probe
+ * walk starts at in a table of `cap` slots (the walk goes on to the next slot, modulo cap), so tests can craft
+ * collisions; the backlog rule: 0 when 2 * backlog_sum <= cap, else EINVAL. */
+uint64_t dk_tcp_listen_key(uint32_t listener, uint32_t remote_ip, uint16_t remote_port);
+uint32_t dk_tcp_listen_home(uint32_t cap, uint64_t key);
+int dk_tcp_listen_backlog_fits(uint32_t cap, uint64_t backlog_sum);
+
+/* rx = the results of the batch's dk_rx_process call (meta, src_ip, ports, payload, flow_id, tcp_seq, tcp_ack, tcp_win
+ * and tcp_opts are required), n its frames; listeners[0 .. nl) with nl <= DK_TCP_LSN_MAX_LISTENERS; link optional.
+ * Returns 0, EINVAL (a null required pointer, misaligned listeners, nl too large, n >= 2^31, out_bytes >
+ * DK_RX_MAX_BLOB, nlinks == 0, the backlog rule: all before any GPU work), ENOMEM or EIO. n == 0 and nl == 0 are valid
+ * calls. */
+int dk_tcp_listen_process(dk_tcp_listen_table* t, const dk_rx_results* rx, uint32_t n, dk_tcp_listener* listeners,
+                          uint32_t nl, uint64_t backlog_sum, const uint32_t* lsn_of_flow, uint32_t nflows,
+                          const uint32_t* link, const dk_tx_link* links, uint32_t nlinks, uint64_t now_ns, uint8_t* out,
+                          uint64_t out_bytes, const dk_tcp_tx_layout* layout, uint32_t max_frames, uint32_t max_ready,
+                          uint32_t flags, const dk_tcp_lsn_results* results, void* stream);
+
+/* Returns as dk_tcp_listen_process (backlog_sum is checked on the host only: the call inserts nothing).
+ * results->action, slot and reply_frame are not used. */
+int dk_tcp_listen_timers(dk_tcp_listen_table* t, const dk_tcp_listener* listeners, uint32_t nl, uint64_t backlog_sum,
+                         const dk_tx_link* links, uint32_t nlinks, uint64_t now_ns, uint8_t* out, uint64_t out_bytes,
+                         const dk_tcp_tx_layout* layout, uint32_t max_frames, uint32_t max_ready, uint32_t flags,
+                         const dk_tcp_lsn_results* results, void* stream);
+
+/* keys[0 .. nkeys): device array of key words; found[nkeys]: device. Returns 0, EINVAL or EIO. */
+int dk_tcp_listen_release(dk_tcp_listen_table* t, dk_tcp_listener* listeners, uint32_t nl, const uint64_t* keys,
+                          uint32_t nkeys, uint32_t* found, void* stream);
 
 #ifdef __cplusplus
 }
