@@ -28,8 +28,12 @@ from .tcp_ackemit import AckEmitResults, ack_emit, ack_emit_batch, ack_timer, da
 from .tcp_cc import CcAckOut, TimersOut, cc_ack, cc_conn_table, cc_send, timers  # noqa: F401
 from .tcp_commit import CommitOut, rtx_piggyback, tx_commit  # noqa: F401
 from .tcp_listen import ListenResults, ListenTable, listen_process, listen_release, listen_timers, listener_table  # noqa: F401
+from .tcp_connect import (ConnectResults, conn_of_flow, conn_rows_from_connect_ready, connect_process, connect_start,  # noqa: F401
+                          connect_timers, connector_table)
 
-__all__ = ["ListenResults", "ListenTable", "listen_process", "listen_release", "listen_timers", "listener_table",
+__all__ = ["ConnectResults", "conn_of_flow", "conn_rows_from_connect_ready", "connect_process", "connect_start",
+           "connect_timers", "connector_table",
+           "ListenResults", "ListenTable", "listen_process", "listen_release", "listen_timers", "listener_table",
            "CommitOut", "rtx_piggyback", "tx_commit", "CcAckOut", "TimersOut", "cc_ack", "cc_conn_table", "cc_send", "timers", "AckEmitResults", "ack_emit", "ack_emit_batch", "ack_timer", "dack_conn_table", "RtxResults", "retransmit", "retransmit_batch", "TcpAcker", "TcpAckOut", "UnackedQueue", "ack_conn_table", "sync_send_next", "PushList", "TcpSender", "TcpTxResults", "tx_conn_table","Comm", "Config", "Fail", "FrameBatch", "RxEngine", "RxResults", "SocketId", "V", "VERDICTS", "flow_array",
            "ipv4", "ipv4_str", "raise_for_verdict", "tx_tuning", "TxSegments", "tx_header_bytes", "tx_links",
            "tx_serialize"]

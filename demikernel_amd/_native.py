@@ -408,6 +408,58 @@ TCP_LISTEN_FUNCTIONS = [
     ("dk_tcp_listen_release", c_int, [c_void_p, c_void_p, c_uint32, c_void_p, c_uint32, c_void_p, c_void_p]),
 ]
 
+# include/dk_tcp.h, the active open (dk_tcp_connect_*)
+DK_TCP_CON_NONE = 0xFFFFFFFF
+DK_TCP_CON_FALLBACK_MSS = 536
+DK_TCP_CON_SYN_BYTES, DK_TCP_CON_ACK_BYTES = 62, 54
+TCP_CON_STATES = ["IDLE", "CONNECTING", "ESTAB", "FAILED", "CLOSED"]
+TCP_CON_ACTIONS = ["SKIP", "ESTABLISHED", "RETRY_SYN", "EXHAUSTED", "REFUSED", "FORWARD", "ORPHANED"]
+TCP_CON_CAUSES = ["CAUSE_NONE", "CAUSE_RST", "CAUSE_EXHAUSTED"]
+TCP_CON_STATUSES = ["OK", "E_ROW", "E_STATE", "E_WSCALE", "E_LINK", "E_SLOT", "NO_ROOM"]
+CONNECTOR_DTYPE = np.dtype([("state", "<u2"), ("err", "<u2"), ("flow_id", "<u4"), ("local_ip", "<u4"),
+                            ("remote_ip", "<u4"), ("local_port", "<u2"), ("remote_port", "<u2"), ("local_isn", "<u4"),
+                            ("receive_window_size", "<u2"), ("advertised_mss", "<u2"), ("window_scale", "u1"),
+                            ("reserved0", "u1"), ("reserved1", "<u2"), ("handshake_retries", "<u4"),
+                            ("syns_left", "<u4"), ("handshake_timeout_ns", "<u8"), ("deadline_ns", "<u8"),
+                            ("ip_word", "<u4"), ("link", "<u4")])
+ISN_GEN_DTYPE = np.dtype([("nonce", "<u4"), ("counter", "<u2"), ("reserved", "<u2")])
+CON_READY_DTYPE = np.dtype([("row", "<u4"), ("err", "<u2"), ("cause", "<u2"), ("frame", "<u4"), ("rcv_nxt", "<u4"),
+                            ("snd_nxt", "<u4"), ("local_window", "<u4"), ("remote_window", "<u4"), ("mss", "<u4"),
+                            ("local_wscale", "u1"), ("remote_wscale", "u1"), ("reserved0", "<u2"), ("reserved1", "<u4"),
+                            ("reserved2", "<u8")])
+assert CONNECTOR_DTYPE.itemsize == 64 and ISN_GEN_DTYPE.itemsize == 8 and CON_READY_DTYPE.itemsize == 48
+TCP_CON_RESULT_FIELDS = ["action", "row", "reply_frame", "off_out", "len_out", "frame_seg", "ready", "status",
+                         "n_frames", "n_ready"]
+
+
+class DkTcpConnector(ctypes.Structure):
+    _fields_ = _mirror(CONNECTOR_DTYPE)
+
+
+class DkTcpIsnGen(ctypes.Structure):
+    _fields_ = _mirror(ISN_GEN_DTYPE)
+
+
+class DkTcpConReady(ctypes.Structure):
+    _fields_ = _mirror(CON_READY_DTYPE)
+
+
+class DkTcpConResults(ctypes.Structure):
+    _fields_ = [(name, c_void_p) for name in TCP_CON_RESULT_FIELDS]
+
+
+TCP_CONNECT_FUNCTIONS = [
+    ("dk_tcp_connect_start", c_int, [c_void_p, c_uint32, c_void_p, c_uint32, c_void_p, c_void_p, c_uint32, c_uint64,
+                                     c_void_p, c_uint64, POINTER(DkTcpTxLayout), c_uint32, c_uint32, c_uint32,
+                                     POINTER(DkTcpConResults), c_void_p]),
+    ("dk_tcp_connect_process", c_int, [POINTER(DkRxResults), c_uint32, c_void_p, c_uint32, c_void_p, c_uint32, c_void_p,
+                                       c_void_p, c_uint32, c_uint64, c_void_p, c_uint64, POINTER(DkTcpTxLayout), c_uint32,
+                                       c_uint32, c_uint32, POINTER(DkTcpConResults), c_void_p]),
+    ("dk_tcp_connect_timers", c_int, [c_void_p, c_uint32, c_void_p, c_uint32, c_uint64, c_void_p, c_uint64,
+                                      POINTER(DkTcpTxLayout), c_uint32, c_uint32, c_uint32, POINTER(DkTcpConResults),
+                                      c_void_p]),
+]
+
 # include/dk_diag.h (diagnostics, not the receive ABI)
 # include/dk_demi.h: delivered frames as demi_sgarray_t (host-side, no GPU work)
 class DemiSgaseg(ctypes.Structure):
@@ -475,6 +527,7 @@ DK_TCP_COMMIT_FORMS = {"conn": 0, "chip": 1}
 
 ALL_FUNCTIONS = (FUNCTIONS + RING_FUNCTIONS + TCP_FUNCTIONS + TCP_ACK_FUNCTIONS + TCP_TX_FUNCTIONS + TCP_RTX_FUNCTIONS +
                  TCP_ACKEMIT_FUNCTIONS + TCP_CC_FUNCTIONS + TCP_COMMIT_FUNCTIONS + TCP_LISTEN_FUNCTIONS +
+                 TCP_CONNECT_FUNCTIONS +
                  DIAG_FUNCTIONS +
                  DEMI_FUNCTIONS + COMM_FUNCTIONS)
 

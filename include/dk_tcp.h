@@ -24,8 +24,9 @@
  * timers have expired are dk_tcp_cc_ack, dk_tcp_timers and dk_tcp_cc_send, the last section: where the sections
  * between say that cwnd is an input or that the host fills fire[], those calls are what computes them on the device.
  * Creating a connection (the passive open: SYN, SYN+ACK, the handshake ACK and its timeout, the backlog) is the
- * dk_tcp_listen_* section at the end.
- * Not modelled: the active open, the closing states (FIN-WAIT-1/2, LAST-ACK etc.), the persist timer, repacketization.
+ * dk_tcp_listen_* section; the active open (the ISN, the SYN and its retries, the tests on the answer, the handshake
+ * ACK) is the dk_tcp_connect_* section at the end.
+ * Not modelled: the closing states (FIN-WAIT-1/2, LAST-ACK etc.), the persist timer, repacketization.
  *
  * Conventions as dk_rx.h: 0 or a positive errno; device pointers; asynchronous on the caller's stream. A context holds
  * one set of scratch buffers: calls on one context are serialised — a call on another stream than the previous call
@@ -826,7 +827,8 @@ int dk_tcp_rtx_piggyback(dk_tcp_tx_ctx* ctx, const dk_tcp_rtx_results* results, 
  * never read. These entry points are additive: DK_RX_ABI_VERSION stays 4.
  * Out of scope: turning a ready record into rows of the five TCP tables and an Active socket-table entry on the device
  * (that needs a link and a queue region, which are the host's to give); feeding FORWARD frames to dk_tcp_rx_process
- * before that entry exists; the active open; FIN-WAIT / LAST-ACK; SYN cookies (the reference has none).
+ * before that entry exists; the active open (the dk_tcp_connect_* section below); FIN-WAIT / LAST-ACK; SYN cookies (the
+ * reference has none).
  * ------------------------------------------------------------------------------------------------------------- */
 #define DK_TCP_LSN_NONE 0xFFFFFFFFu
 #define DK_TCP_LSN_NO_WSCALE 0xFFu
@@ -990,6 +992,223 @@ int dk_tcp_listen_timers(dk_tcp_listen_table* t, const dk_tcp_listener* listener
 /* keys[0 .. nkeys): device array of key words; found[nkeys]: device. Returns 0, EINVAL or EIO. */
 int dk_tcp_listen_release(dk_tcp_listen_table* t, dk_tcp_listener* listeners, uint32_t nl, const uint64_t* keys,
                           uint32_t nkeys, uint32_t* found, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * The active open: what TcpPeer::connect (peer.rs:149-179) and SharedActiveOpenSocket (active_open.rs: process_ack
+ * :101-223, connect :225-294, close :296-298) do for a connecting socket, from the ISN to the arguments of
+ * EstablishedSocket::new. A connecting socket is a row of dk_tcp_connector in device memory; there is no hash table:
+ * the socket table already maps the 4-tuple to a flow id (a DK_FLOW_TCP_ACTIVE entry), and conn_of_flow[nflows] maps a
+ * flow id to its connector row, DK_TCP_CON_NONE for every other flow. The peer's one IsnGenerator (peer.rs:171) is a
+ * dk_tcp_isn_gen in device memory.
+ *
+ * dk_tcp_connect_start is connect() up to its first await. start[0 .. nstart) names rows in connect-call order. Entry k
+ * takes the counter value counter + k (wrapping u16) whatever becomes of its row (the reference generates the ISN before
+ * anything can fail), and the generator ends at counter + nstart. local_isn = crc + that value (wrapping u32), crc being
+ * the CRC-32/CKSUM of the listen section over the same 16 bytes: the remote ip's octets, the remote port big-endian, the
+ * local ip's octets, the local port big-endian, the nonce big-endian. Row checks, the first that applies (status[k]; a
+ * row that fails one is left untouched):
+ *   E_ROW     start[k] >= nrows
+ *   E_STATE   the row is not IDLE, or an earlier entry of start[] names the same row (the lowest k wins)
+ *   E_WSCALE  window_scale > 14
+ *   E_LINK    link >= nlinks
+ *   E_SLOT    frame_lead + 62 > slot_stride
+ * A row with handshake_retries == 0 sends nothing: it becomes FAILED / ECONNREFUSED (the loop body never runs, this is
+ * connect()'s last line) with an error ready record of cause EXHAUSTED. Every other row becomes CONNECTING with
+ * local_isn set, syns_left = handshake_retries - 1 and deadline_ns = now_ns + handshake_timeout_ns, and a SYN goes out.
+ * handshake_retries therefore counts SYNs in all, as in the reference (connect-refused.pkt: 5 gives five SYNs).
+ * SYNs are numbered in start[] order; frame_seg holds k, and so does `frame` of the error records. The per-frame
+ * results (action, row, reply_frame) are not used.
+ *
+ * dk_tcp_connect_process covers the frames of one dk_rx_process batch with verdict DK_V_OK_TCP whose flow_id maps to a
+ * connector row; every other frame gets action SKIP. Frames are taken in arrival order per row, and each coroutine is
+ * taken to have run to its next await before the next frame arrives (the listen section's assumption). By the row's
+ * state:
+ *   CONNECTING   process_ack (:101-126), in its order:
+ *                  1. !(ack && ack_num == local_isn + 1): EAGAIN
+ *                  2. rst: refused (a RST whose ack does not match is only an EAGAIN; SYN+RST with a matching ack is
+ *                     refused)
+ *                  3. !syn: EAGAIN
+ *                  4. otherwise accepted.
+ *                EAGAIN is the loop's `continue`, the same as a timeout: with syns_left > 0 a SYN goes out again,
+ *                syns_left -= 1, deadline_ns = now_ns + handshake_timeout_ns, action RETRY_SYN; with syns_left == 0 the
+ *                row becomes FAILED / ECONNREFUSED, action EXHAUSTED, an error ready record of cause EXHAUSTED, no reply.
+ *                That a stray segment costs a retry is the reference's quirk; it is kept.
+ *                Refused: FAILED / ECONNREFUSED, action REFUSED, an error ready record of cause RST, no reply.
+ *                Accepted: action ESTABLISHED, the row becomes ESTABLISHED, the handshake ACK goes out and a ready
+ *                record is appended. A payload on the SYN+ACK is dropped: connect() discards the buffer (:276), unlike
+ *                the passive side.
+ *   ESTABLISHED  (already, or by an earlier frame of this batch) action FORWARD: recv_queue is shared with the
+ *                established socket, the host routes the frame by row[].
+ *   FAILED       (already, or earlier in this batch) action ORPHANED: the reference removes the address entry, which is
+ *                the host's job.
+ *   IDLE, CLOSED SKIP. A host that closes a connecting socket (close(), ECONNABORTED) writes state = CLOSED between
+ *                calls; no entry point is needed.
+ * Negotiation (:150-194), in the ready record: mss = the frame's last MaximumSegmentSize entry, else
+ * DK_TCP_CON_FALLBACK_MSS; with a WindowScale entry remote_wscale = the last one's value capped at 14 and local_wscale =
+ * window_scale, without one both are 0; local_window = receive_window_size << local_wscale; remote_window = the header
+ * window << remote_wscale. The reference passes congestion_control::None::new here (:218): the host chooses the CC row,
+ * as it does after a passive open.
+ * Frames are the bytes dk_tx_serialize writes for the same descriptor with an empty payload; DK_TX_OFFLOAD_TCP in
+ * `flags` writes the TCP checksum as 0, as in the listen section. Source = the row's local address, destination its
+ * remote; ip_word is the row's; the link is link[i] when a per-frame link[] is given and link[i] < nlinks
+ * (dk_tcp_connect_process only), else the row's.
+ *   SYN  62 bytes: flags SYN, seq = local_isn, ack 0, window = receive_window_size, options [MSS(advertised_mss),
+ *        WindowScale(window_scale)].
+ *   ACK  54 bytes: flags ACK, seq = local_isn + 1, ack = seq_num + 1, window = receive_window_size unscaled, no options.
+ * Replies are numbered in the order of the frames that triggered them; reply f owns slot f under dk_tcp_tx_layout's
+ * rule; no byte of out outside the frames is written. Ready records follow the order of the frames that made them.
+ * status[r], r < nrows: a CONNECTING row reports the first of E_WSCALE, E_LINK, E_SLOT that applies (its frames are
+ * SKIP, nothing of it changes); every other row reports OK.
+ *
+ * dk_tcp_connect_timers is the pop's timeout (:275, :281): every CONNECTING row that passes the checks with deadline_ns
+ * <= now_ns takes the EAGAIN step above. Frames and ready records come in ascending row order; frame_seg holds the row,
+ * `frame` of the records is DK_TCP_CON_NONE. The per-frame results are not used; status[] as in dk_tcp_connect_process.
+ *
+ * Capacity is all or nothing and tested on the device, in all three calls: n_frames and n_ready always report the
+ * call's need; if n_frames > max_frames, or n_frames * slot_stride > out_bytes, or n_ready > max_ready, then nothing
+ * else is written (no frame, record, per-frame result, row field or generator field) and NO_ROOM is reported by the
+ * rows that had a frame other than SKIP (process), the rows that were due (timers), the entries that passed their
+ * checks (start). There is no host round trip anywhere in a call.
+ * The outcome for a row in dk_tcp_connect_process is a function of the index of its first refused / accepted frame, the
+ * arrival rank of its EAGAIN frames before that, and syns_left. A count and a 32-bit minimum per row settle the rows
+ * with one frame, a second count and minimum the rows with two frames up to that first refused / accepted one; the
+ * frames of rows with three or more are compacted in frame order and ranked per row exactly, for any number of frames
+ * per row: a wave groups each 64 of them by row, the groups of a row are chained, and a group's base is the sum over
+ * the row's groups before it. The memory is a word per row and a few per frame.
+ *
+ * The calls take their scratch from one per-device pool of the library (the current device's) and are serialised on it
+ * as a context's calls are; asynchronous on the caller's stream; the environment is never read. These entry points are
+ * additive: DK_RX_ABI_VERSION stays 4.
+ * Out of scope: the ephemeral-port allocator and the socket table's Active entry (the host's, before
+ * dk_tcp_connect_start) and its removal on failure; ARP resolution before the first SYN; building the rows of the five
+ * TCP tables on the device; FIN-WAIT / LAST-ACK; simultaneous open (the reference has none).
+ * ------------------------------------------------------------------------------------------------------------- */
+#define DK_TCP_CON_NONE 0xFFFFFFFFu
+#define DK_TCP_CON_FALLBACK_MSS 536u         /* FALLBACK_MSS (tcp/constants.rs)                                     */
+#define DK_TCP_CON_SYN_BYTES 62u
+#define DK_TCP_CON_ACK_BYTES 54u
+
+enum dk_tcp_con_state {
+    DK_TCP_CON_IDLE = 0,        /* bound to its addresses, not yet started                                          */
+    DK_TCP_CON_CONNECTING = 1,
+    DK_TCP_CON_ESTAB = 2,
+    DK_TCP_CON_FAILED = 3,      /* err = ECONNREFUSED                                                               */
+    DK_TCP_CON_CLOSED = 4       /* written by the host: close() while connecting                                    */
+};
+
+/* One connecting socket. Device memory, 16-byte aligned, updated in place (state, err, local_isn, syns_left,
+ * deadline_ns). */
+typedef struct dk_tcp_connector {
+    uint16_t state;                /* enum dk_tcp_con_state                                                        */
+    uint16_t err;                  /* 0 or ECONNREFUSED                                                            */
+    uint32_t flow_id;              /* its index in the socket table (informational: conn_of_flow is what is used)  */
+    uint32_t local_ip;             /* octet order, as dk_rx.h                                                      */
+    uint32_t remote_ip;
+    uint16_t local_port;
+    uint16_t remote_port;
+    uint32_t local_isn;            /* written by dk_tcp_connect_start                                              */
+    uint16_t receive_window_size;  /* TcpConfig::get_receive_window_size                                           */
+    uint16_t advertised_mss;
+    uint8_t window_scale;          /* TcpConfig::get_window_scale                                                  */
+    uint8_t reserved0;
+    uint16_t reserved1;
+    uint32_t handshake_retries;    /* SYNs in all                                                                  */
+    uint32_t syns_left;            /* SYNs the loop may still send                                                 */
+    uint64_t handshake_timeout_ns;
+    uint64_t deadline_ns;          /* the pending pop's timeout                                                    */
+    uint32_t ip_word;              /* dk_tx_segs.ip_word of the frames                                             */
+    uint32_t link;                 /* index into links[]                                                           */
+} dk_tcp_connector;                /* 64 bytes */
+
+/* The peer's IsnGenerator. Device memory, 8-byte aligned. */
+typedef struct dk_tcp_isn_gen {
+    uint32_t nonce;
+    uint16_t counter;
+    uint16_t reserved;
+} dk_tcp_isn_gen;
+
+enum dk_tcp_con_action {
+    DK_TCP_CON_SKIP = 0,
+    DK_TCP_CON_ESTABLISHED = 1,
+    DK_TCP_CON_RETRY_SYN = 2,
+    DK_TCP_CON_EXHAUSTED = 3,
+    DK_TCP_CON_REFUSED = 4,
+    DK_TCP_CON_FORWARD = 5,
+    DK_TCP_CON_ORPHANED = 6
+};
+
+enum dk_tcp_con_cause { DK_TCP_CON_CAUSE_NONE = 0, DK_TCP_CON_CAUSE_RST = 1, DK_TCP_CON_CAUSE_EXHAUSTED = 2 };
+
+/* A ready record: what EstablishedSocket::new gets (:201-222), or the error connect() returns. An error record carries
+ * row, err, cause, frame and snd_nxt; its other fields are 0. */
+typedef struct dk_tcp_con_ready {
+    uint32_t row;
+    uint16_t err;            /* 0 or ECONNREFUSED                                                                  */
+    uint16_t cause;          /* enum dk_tcp_con_cause                                                              */
+    uint32_t frame;          /* the triggering batch frame; the start[] entry (dk_tcp_connect_start); DK_TCP_CON_NONE
+                                from dk_tcp_connect_timers                                                         */
+    uint32_t rcv_nxt;        /* seq_num + 1                                                                        */
+    uint32_t snd_nxt;        /* local_isn + 1                                                                      */
+    uint32_t local_window;   /* receive_window_size << local_wscale                                                */
+    uint32_t remote_window;  /* the SYN+ACK's header window << remote_wscale                                       */
+    uint32_t mss;
+    uint8_t local_wscale;
+    uint8_t remote_wscale;
+    uint16_t reserved0;
+    uint32_t reserved1;
+    uint64_t reserved2;
+} dk_tcp_con_ready;          /* 48 bytes */
+
+enum dk_tcp_con_status {
+    DK_TCP_CON_OK = 0,
+    DK_TCP_CON_E_ROW = 1,
+    DK_TCP_CON_E_STATE = 2,
+    DK_TCP_CON_E_WSCALE = 3,
+    DK_TCP_CON_E_LINK = 4,
+    DK_TCP_CON_E_SLOT = 5,
+    DK_TCP_CON_NO_ROOM = 6
+};
+
+/* Outputs (device). Per batch frame, [n] (dk_tcp_connect_process only): action (enum dk_tcp_con_action), row (the
+ * connector row for every action but SKIP, else DK_TCP_CON_NONE), reply_frame (its reply's frame index or
+ * DK_TCP_CON_NONE). Per reply, [max_frames]: off_out, len_out (a dk_rx_batch over `out`), frame_seg (optional: see each
+ * call). ready: [max_ready]. status: [nrows] (dk_tcp_connect_start: [nstart]), enum dk_tcp_con_status. n_frames,
+ * n_ready: one word each, the call's need. */
+typedef struct dk_tcp_con_results {
+    uint8_t* action;
+    uint32_t* row;
+    uint32_t* reply_frame;
+    uint32_t* off_out;
+    uint16_t* len_out;
+    uint32_t* frame_seg;
+    dk_tcp_con_ready* ready;
+    uint32_t* status;
+    uint32_t* n_frames;
+    uint32_t* n_ready;
+} dk_tcp_con_results;
+
+/* start[0 .. nstart): device array of row indices. Returns 0, EINVAL (a null required pointer, misaligned rows or
+ * isn_gen, nstart >= 2^31, out_bytes > DK_RX_MAX_BLOB, nlinks == 0: all before any GPU work), ENOMEM or EIO. nstart == 0
+ * and nrows == 0 are valid calls. */
+int dk_tcp_connect_start(dk_tcp_connector* rows, uint32_t nrows, const uint32_t* start, uint32_t nstart,
+                         dk_tcp_isn_gen* isn_gen, const dk_tx_link* links, uint32_t nlinks, uint64_t now_ns, uint8_t* out,
+                         uint64_t out_bytes, const dk_tcp_tx_layout* layout, uint32_t max_frames, uint32_t max_ready,
+                         uint32_t flags, const dk_tcp_con_results* results, void* stream);
+
+/* rx = the results of the batch's dk_rx_process call (meta, flow_id, tcp_seq, tcp_ack, tcp_win and tcp_opts are
+ * required), n its frames; link optional. Returns as dk_tcp_connect_start (n >= 2^31 is EINVAL). n == 0 and nrows == 0
+ * are valid calls. */
+int dk_tcp_connect_process(const dk_rx_results* rx, uint32_t n, dk_tcp_connector* rows, uint32_t nrows,
+                           const uint32_t* conn_of_flow, uint32_t nflows, const uint32_t* link, const dk_tx_link* links,
+                           uint32_t nlinks, uint64_t now_ns, uint8_t* out, uint64_t out_bytes,
+                           const dk_tcp_tx_layout* layout, uint32_t max_frames, uint32_t max_ready, uint32_t flags,
+                           const dk_tcp_con_results* results, void* stream);
+
+/* Returns as dk_tcp_connect_start. results->action, row and reply_frame are not used. */
+int dk_tcp_connect_timers(dk_tcp_connector* rows, uint32_t nrows, const dk_tx_link* links, uint32_t nlinks,
+                          uint64_t now_ns, uint8_t* out, uint64_t out_bytes, const dk_tcp_tx_layout* layout,
+                          uint32_t max_frames, uint32_t max_ready, uint32_t flags, const dk_tcp_con_results* results,
+                          void* stream);
 
 #ifdef __cplusplus
 }
