@@ -30,8 +30,10 @@ from .tcp_commit import CommitOut, rtx_piggyback, tx_commit  # noqa: F401
 from .tcp_listen import ListenResults, ListenTable, listen_process, listen_release, listen_timers, listener_table  # noqa: F401
 from .tcp_connect import (ConnectResults, conn_of_flow, conn_rows_from_connect_ready, connect_process, connect_start,  # noqa: F401
                           connect_timers, connector_table)
+from .tcp_close import CloseResults, close_process, close_start, close_timers, closer_table  # noqa: F401
 
-__all__ = ["ConnectResults", "conn_of_flow", "conn_rows_from_connect_ready", "connect_process", "connect_start",
+__all__ = ["CloseResults", "close_process", "close_start", "close_timers", "closer_table",
+           "ConnectResults", "conn_of_flow", "conn_rows_from_connect_ready", "connect_process", "connect_start",
            "connect_timers", "connector_table",
            "ListenResults", "ListenTable", "listen_process", "listen_release", "listen_timers", "listener_table",
            "CommitOut", "rtx_piggyback", "tx_commit", "CcAckOut", "TimersOut", "cc_ack", "cc_conn_table", "cc_send", "timers", "AckEmitResults", "ack_emit", "ack_emit_batch", "ack_timer", "dack_conn_table", "RtxResults", "retransmit", "retransmit_batch", "TcpAcker", "TcpAckOut", "UnackedQueue", "ack_conn_table", "sync_send_next", "PushList", "TcpSender", "TcpTxResults", "tx_conn_table","Comm", "Config", "Fail", "FrameBatch", "RxEngine", "RxResults", "SocketId", "V", "VERDICTS", "flow_array",

@@ -460,6 +460,46 @@ TCP_CONNECT_FUNCTIONS = [
                                       c_void_p]),
 ]
 
+# include/dk_tcp.h, closing a connection (dk_tcp_close_*)
+DK_TCP_CLS_NONE = 0xFFFFFFFF
+DK_TCP_CLS_TIME_WAIT_NS = 4_000_000_000
+DK_TCP_CLS_RETIRED = 1
+DK_TCP_CLS_ACK_BYTES = 54
+TCP_CLS_STATES = ["IDLE", "FIN_WAIT_1", "FIN_WAIT_2", "CLOSING", "TIME_WAIT", "LAST_ACK", "CLOSED", "FAULT"]
+TCP_CLS_ACTION_BITS = {"POPPED": 1, "ACK_OK": 2, "ACK_UNSENT": 4, "FIN": 8, "FAULT_BIT": 16, "UNPROCESSED": 32}
+TCP_CLS_STATUSES = ["OK", "E_ROW", "E_ORDER", "E_STATE", "E_BADF", "E_RX_STATE", "E_LINK", "E_WSCALE", "E_WINDOW",
+                    "E_SLOT", "NO_ROOM"]
+CLOSER_DTYPE = np.dtype([("state", "<u2"), ("err", "<u2"), ("flags", "<u4"), ("linger_ns", "<u8"),
+                         ("deadline_ns", "<u8"), ("reserved", "<u8")])
+CLS_DONE_DTYPE = np.dtype([("row", "<u4"), ("state", "<u2"), ("err", "<u2"), ("frame", "<u4"), ("fin_frame", "<u4"),
+                           ("deadline_ns", "<u8"), ("reserved", "<u8")])
+assert CLOSER_DTYPE.itemsize == 32 and CLS_DONE_DTYPE.itemsize == 32
+TCP_CLS_RESULT_FIELDS = ["action", "state_after", "ack_action", "reply_frame", "off_out", "len_out", "frame_seg", "done",
+                         "status", "fin_frame", "n_frames", "n_done"]
+
+
+class DkTcpCloser(ctypes.Structure):
+    _fields_ = _mirror(CLOSER_DTYPE)
+
+
+class DkTcpClsDone(ctypes.Structure):
+    _fields_ = _mirror(CLS_DONE_DTYPE)
+
+
+class DkTcpClsResults(ctypes.Structure):
+    _fields_ = [(name, c_void_p) for name in TCP_CLS_RESULT_FIELDS]
+
+
+TCP_CLOSE_FUNCTIONS = [
+    ("dk_tcp_close_start", c_int, [c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_uint32, c_void_p, c_void_p,
+                                   c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("dk_tcp_close_process", c_int, [POINTER(DkRxResults), c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32,
+                                     c_void_p, c_void_p, c_uint32, c_uint64, c_void_p, c_uint64, POINTER(DkTcpTxLayout),
+                                     c_uint32, c_uint32, c_uint32, POINTER(DkTcpClsResults), c_void_p]),
+    ("dk_tcp_close_timers", c_int, [c_void_p, c_void_p, c_uint32, c_uint64, c_void_p, c_uint32, c_void_p, c_void_p,
+                                    c_void_p]),
+]
+
 # include/dk_diag.h (diagnostics, not the receive ABI)
 # include/dk_demi.h: delivered frames as demi_sgarray_t (host-side, no GPU work)
 class DemiSgaseg(ctypes.Structure):
@@ -527,7 +567,7 @@ DK_TCP_COMMIT_FORMS = {"conn": 0, "chip": 1}
 
 ALL_FUNCTIONS = (FUNCTIONS + RING_FUNCTIONS + TCP_FUNCTIONS + TCP_ACK_FUNCTIONS + TCP_TX_FUNCTIONS + TCP_RTX_FUNCTIONS +
                  TCP_ACKEMIT_FUNCTIONS + TCP_CC_FUNCTIONS + TCP_COMMIT_FUNCTIONS + TCP_LISTEN_FUNCTIONS +
-                 TCP_CONNECT_FUNCTIONS +
+                 TCP_CONNECT_FUNCTIONS + TCP_CLOSE_FUNCTIONS +
                  DIAG_FUNCTIONS +
                  DEMI_FUNCTIONS + COMM_FUNCTIONS)
 

@@ -26,7 +26,9 @@
  * Creating a connection (the passive open: SYN, SYN+ACK, the handshake ACK and its timeout, the backlog) is the
  * dk_tcp_listen_* section; the active open (the ISN, the SYN and its retries, the tests on the answer, the handshake
  * ACK) is the dk_tcp_connect_* section at the end.
- * Not modelled: the closing states (FIN-WAIT-1/2, LAST-ACK etc.), the persist timer, repacketization.
+ * Ending a connection (ControlBlock::close: FIN-WAIT-1/2, CLOSING, TIME-WAIT and LAST-ACK over the segments that arrive
+ * after poll() has returned) is the dk_tcp_close_* section, the last one.
+ * Not modelled: the persist timer, repacketization.
  *
  * Conventions as dk_rx.h: 0 or a positive errno; device pointers; asynchronous on the caller's stream. A context holds
  * one set of scratch buffers: calls on one context are serialised — a call on another stream than the previous call
@@ -827,7 +829,7 @@ int dk_tcp_rtx_piggyback(dk_tcp_tx_ctx* ctx, const dk_tcp_rtx_results* results, 
  * never read. These entry points are additive: DK_RX_ABI_VERSION stays 4.
  * Out of scope: turning a ready record into rows of the five TCP tables and an Active socket-table entry on the device
  * (that needs a link and a queue region, which are the host's to give); feeding FORWARD frames to dk_tcp_rx_process
- * before that entry exists; the active open (the dk_tcp_connect_* section below); FIN-WAIT / LAST-ACK; SYN cookies (the
+ * before that entry exists; the active open (the dk_tcp_connect_* section below); the closing states (the dk_tcp_close_* section); SYN cookies (the
  * reference has none).
  * ------------------------------------------------------------------------------------------------------------- */
 #define DK_TCP_LSN_NONE 0xFFFFFFFFu
@@ -1081,7 +1083,7 @@ int dk_tcp_listen_release(dk_tcp_listen_table* t, dk_tcp_listener* listeners, ui
  * additive: DK_RX_ABI_VERSION stays 4.
  * Out of scope: the ephemeral-port allocator and the socket table's Active entry (the host's, before
  * dk_tcp_connect_start) and its removal on failure; ARP resolution before the first SYN; building the rows of the five
- * TCP tables on the device; FIN-WAIT / LAST-ACK; simultaneous open (the reference has none).
+ * TCP tables on the device; the closing states (the dk_tcp_close_* section); simultaneous open (the reference has none).
  * ------------------------------------------------------------------------------------------------------------- */
 #define DK_TCP_CON_NONE 0xFFFFFFFFu
 #define DK_TCP_CON_FALLBACK_MSS 536u         /* FALLBACK_MSS (tcp/constants.rs)                                     */
@@ -1209,6 +1211,198 @@ int dk_tcp_connect_timers(dk_tcp_connector* rows, uint32_t nrows, const dk_tx_li
                           uint64_t now_ns, uint8_t* out, uint64_t out_bytes, const dk_tcp_tx_layout* layout,
                           uint32_t max_frames, uint32_t max_ready, uint32_t flags, const dk_tcp_con_results* results,
                           void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Closing a connection: ControlBlock::close with local_close and remote_already_closed (established/ctrlblk.rs:
+ * 1039-1119), for every closing connection of a batch at once. A closing connection is a row of dk_tcp_closer in device
+ * memory, indexed by flow id like the five TCP tables. Sending the FIN (a zero-length push through dk_tcp_tx_segment,
+ * queued by dk_tcp_tx_commit, resent by dk_tcp_retransmit) and receiving one in ESTABLISHED (dk_tcp_rx_process's
+ * DK_TCP_FIN, acknowledged by dk_tcp_ack_emit) exist already; this section is the coroutine that pops recv_queue itself
+ * once poll() has stopped (:350-372): no window check, no RST or SYN check, no data processing.
+ *
+ * dk_tcp_close_start is close() up to its first await (:1040-1057). close[0 .. nclose) names connections. Per entry k,
+ * the first of these that applies gives status[k] (a rejected entry changes nothing):
+ *   E_ROW    close[k] >= nconns
+ *   E_ORDER  close[k] <= the maximum of close[0 .. k): the list must be strictly ascending, because the marker list it
+ *            yields must have non-decreasing conn
+ *   E_STATE  tx_conns[c].state != DK_TCP_ESTABLISHED
+ *   E_BADF   the row is not IDLE, or rx_conns[c].state is DK_TCP_NONE ("socket is already closing", EBADF)
+ * An accepted entry whose rx state is ESTABLISHED makes the row FIN_WAIT_1 and sets rx_conns[c].state = DK_TCP_CLOSED,
+ * as poll() has returned; one whose rx state is CLOSED (a FIN or an RST was received earlier: CloseWait) makes the row
+ * LAST_ACK. err = 0, flags = 0, deadline_ns = 0; linger_ns is the caller's input. The accepted connections are written
+ * to push_conn[0 .. *n_markers) in order with push_off = push_len = 0; the tail up to nclose is padded with conn =
+ * 0xFFFFFFFF, off = len = 0. The three arrays with nbufs = nclose are a valid dk_tcp_tx_push for dk_tcp_tx_segment: the
+ * padding reports DK_TCP_TX_E_CONN and sends nothing, so the FIN goes out without the host reading a status. Merging the
+ * markers into a call that also carries data stays with the caller.
+ *
+ * dk_tcp_close_process covers the frames of one dk_rx_process batch with verdict DK_V_OK_TCP whose flow id is below
+ * nconns and whose row is in FIN_WAIT_1, FIN_WAIT_2, CLOSING or LAST_ACK (a live row) and passes the row checks; every
+ * other frame is SKIP (action 0). Row checks, the first that applies (status[c]; the row's frames are SKIP and nothing of
+ * it changes; every row that is not live reports OK):
+ *   E_RX_STATE  rx_conns[c].state != DK_TCP_CLOSED
+ *   E_STATE     tx_conns[c].state != DK_TCP_ESTABLISHED
+ *   E_LINK, E_WSCALE, E_WINDOW, E_SLOT  exactly as dk_tcp_ack_emit states them
+ * A live row's frames are taken in arrival order. snd_nxt = tx_conns[c].snd_nxt does not move during a call, so three
+ * bits of the frame alone decide: A = ACK set and ack <= snd_nxt (the sign of the wrapping difference), U = ACK set and
+ * ack > snd_nxt, F = FIN. Per popped frame, process_ack (:607-650) first: A is Ok, U sends an ACK of ours and is Err, no
+ * ACK bit is Err; then, in the local_close loop and also after an Err, process_remote_close (:1003-1026):
+ *   state before  A  F  state after  side effects
+ *   FIN_WAIT_1    0  0  FIN_WAIT_1   an ACK of ours if U
+ *   FIN_WAIT_1    1  0  FIN_WAIT_2   ACK-processed
+ *   FIN_WAIT_1    0  1  CLOSING      an ACK if U; FIN consumed
+ *   FIN_WAIT_1    1  1  TIME_WAIT    ACK-processed; FIN consumed
+ *   FIN_WAIT_2    x  0  FIN_WAIT_2   ACK-processed if A; an ACK if U
+ *   FIN_WAIT_2    x  1  TIME_WAIT    as above; FIN consumed
+ *   CLOSING       0  0  CLOSING      an ACK if U
+ *   CLOSING       1  0  TIME_WAIT    ACK-processed
+ *   CLOSING       x  1  FAULT        the deviation below
+ *   LAST_ACK      0  x  LAST_ACK     an ACK if U; F ignored
+ *   LAST_ACK      1  x  CLOSED       ACK-processed; F ignored
+ * Two quirks of the reference are kept: any acceptable ACK takes FIN_WAIT_1 to FIN_WAIT_2, whether or not it covers our
+ * FIN; and the FIN's sequence number is not looked at. TIME_WAIT, CLOSED and FAULT end the row's loop: its later frames
+ * of the batch are never popped (action UNPROCESSED). "FIN consumed" is RCV.NXT += 1 and one ACK of ours carrying the
+ * new RCV.NXT; a consumed frame with U sends two ACKs, the first with the old RCV.NXT. A row changes state at most twice
+ * in a call and RCV.NXT moves at most once.
+ * One stated deviation: CLOSING + F panics the reference (unreachable!, :1087) after process_remote_close has run its
+ * side effects. Here that frame gets action FAULT alone and nothing of it is applied: no ACK, RCV.NXT stays, its
+ * ack_action is DK_TCP_UNPROCESSED; the row becomes DK_TCP_CLS_FAULT with err = EPROTO and a done record is appended.
+ * Per-frame outputs: action (the DK_TCP_CLS_* bits below), state_after (the row's state after a popped or FAULT frame,
+ * its final state for an UNPROCESSED one, 0 for SKIP), reply_frame (the index of the frame's first ACK, or
+ * DK_TCP_CLS_NONE), and ack_action in enum dk_tcp_action codes: the array to hand to dk_tcp_cc_ack and
+ * dk_tcp_ack_process in place of the receive call's `action`, so that those kernels do the rest of process_ack
+ * (on_ack_received, SND.UNA, the send window, the unacknowledged queue with the FIN marker's pop, the RTT sample and the
+ * retransmit deadline). A popped frame gets DK_TCP_NO_DATA for A, DK_TCP_ACK_UNSENT for U, DK_TCP_NO_ACK for neither; a
+ * frame of a live row that was not popped gets DK_TCP_UNPROCESSED; every other frame copies action_in[i] (that batch's
+ * dk_tcp_out.action), or is DK_TCP_SKIP without action_in. dk_tcp_ack_emit keeps getting the original action: the two
+ * arrays are distinct. Both of those calls take `action` as a plain input and order the frames from the context's
+ * scratch, which holds the frames of CLOSED connections too.
+ * ACKs of ours are the 54-byte frame dk_tcp_ack_emit builds: seq = tx_conns[c].snd_nxt, ack = RCV.NXT and window =
+ * (buffer_size - (RCV.NXT - reader_next)) >> rcv_wscale as they stood at that moment, DK_TX_OFFLOAD_TCP honoured. They
+ * are numbered in the order of the triggering frames, within a frame the U ACK before the FIN ACK; reply f owns slot f
+ * under dk_tcp_tx_layout's rule; no byte of out outside the frames is written.
+ * Row effects: state and err; deadline_ns = now_ns + linger_ns (wrapping) on entering TIME_WAIT;
+ * rx_conns[c].receive_next += 1 on a consumed FIN; dack[c].armed = 0 (when dack is given) for a row that sent any ACK
+ * (emit, :761); fin_frame[c] = the frame whose FIN was consumed, else DK_TCP_CLS_NONE, for every row; one done record
+ * per row that reached TIME_WAIT, CLOSED or FAULT, in the order of the triggering frames. tx_conns is only read:
+ * retiring the connection here would make the dk_tcp_ack_process that follows reject it.
+ * A row's loop ends after at most two transitions, and each is "the first frame after index t that triggers one from
+ * state s": one classify pass computes row and A / U / F, at most two rounds of a 32-bit minimum per row find the two
+ * frames exactly for any number of frames per row, and every frame's state-before follows from comparing its index with
+ * them. No sort is needed.
+ *
+ * dk_tcp_close_timers is TIME-WAIT's end (yield_with_timeout(linger.unwrap_or(2 * MSL)), :1096-1098) and the retiring
+ * of closed rows: every TIME_WAIT row with deadline_ns <= now_ns becomes CLOSED; every CLOSED row without
+ * DK_TCP_CLS_RETIRED gets it, a done record (frame and fin_frame DK_TCP_CLS_NONE) in ascending row order and, with
+ * tx_conns given, tx_conns[c].state = DK_TCP_CLOSED. status[c] is OK, or NO_ROOM for the rows that had a record.
+ *
+ * Capacity is all or nothing and tested on the device: n_frames and n_done always report the call's need; if n_frames >
+ * max_frames, or n_frames * slot_stride > out_bytes, or n_done > max_done, nothing else is written and the rows that had
+ * work (a live row with a frame in the batch; a row with a record) report NO_ROOM.
+ * The calls take their scratch from a per-device pool of their own and are serialised on it as the connect section's
+ * are; asynchronous on the caller's stream; the environment is never read. These entry points are additive:
+ * DK_RX_ABI_VERSION stays 4.
+ * Out of scope: re-presenting the segments an earlier batch left UNPROCESSED (the reference pops them from recv_queue
+ * first; here the host hands them in again); data received in FIN-WAIT (the reference has a TODO there); removing the
+ * socket-table entry and the listener's close queue; RST generation.
+ * ------------------------------------------------------------------------------------------------------------- */
+#define DK_TCP_CLS_NONE 0xFFFFFFFFu
+#define DK_TCP_CLS_TIME_WAIT_NS 4000000000ull /* 2 * MSL, MSL = 2 s (runtime/network/consts.rs:25)                  */
+#define DK_TCP_CLS_RETIRED 1u                 /* dk_tcp_closer.flags: dk_tcp_close_timers has reported the row      */
+#define DK_TCP_CLS_ACK_BYTES 54u
+
+enum dk_tcp_cls_state {
+    DK_TCP_CLS_IDLE = 0,
+    DK_TCP_CLS_FIN_WAIT_1 = 1,
+    DK_TCP_CLS_FIN_WAIT_2 = 2,
+    DK_TCP_CLS_CLOSING = 3,
+    DK_TCP_CLS_TIME_WAIT = 4,
+    DK_TCP_CLS_LAST_ACK = 5,
+    DK_TCP_CLS_CLOSED = 6,
+    DK_TCP_CLS_FAULT = 7        /* err = EPROTO                                                                      */
+};
+
+/* One closing connection. Device memory, 16-byte aligned, updated in place (state, err, flags, deadline_ns). */
+typedef struct dk_tcp_closer {
+    uint16_t state;        /* enum dk_tcp_cls_state                                                                 */
+    uint16_t err;          /* 0 or EPROTO                                                                           */
+    uint32_t flags;        /* DK_TCP_CLS_RETIRED                                                                    */
+    uint64_t linger_ns;    /* TIME-WAIT's length (input): the socket's linger, else DK_TCP_CLS_TIME_WAIT_NS         */
+    uint64_t deadline_ns;  /* TIME-WAIT's end                                                                       */
+    uint64_t reserved;
+} dk_tcp_closer;           /* 32 bytes */
+
+/* A done record: a row reached TIME_WAIT, CLOSED or FAULT (dk_tcp_close_process), or was retired
+ * (dk_tcp_close_timers). */
+typedef struct dk_tcp_cls_done {
+    uint32_t row;
+    uint16_t state;        /* enum dk_tcp_cls_state                                                                 */
+    uint16_t err;
+    uint32_t frame;        /* the triggering batch frame; DK_TCP_CLS_NONE from dk_tcp_close_timers                  */
+    uint32_t fin_frame;    /* the frame whose FIN was consumed in this call, or DK_TCP_CLS_NONE                     */
+    uint64_t deadline_ns;  /* the row's, after the call                                                             */
+    uint64_t reserved;
+} dk_tcp_cls_done;         /* 32 bytes */
+
+/* dk_tcp_cls_results.action, a bit set; 0 is SKIP. */
+#define DK_TCP_CLS_POPPED 1u       /* the coroutine popped the frame                                                */
+#define DK_TCP_CLS_ACK_OK 2u       /* A: process_ack returned Ok                                                    */
+#define DK_TCP_CLS_ACK_UNSENT 4u   /* U: an ACK of ours went out                                                    */
+#define DK_TCP_CLS_FIN 8u          /* the frame's FIN was consumed                                                  */
+#define DK_TCP_CLS_FAULT_BIT 16u   /* CLOSING + F: nothing of the frame applied, the row is FAULT                   */
+#define DK_TCP_CLS_UNPROCESSED 32u /* a live row's frame behind the frame that ended its loop                       */
+
+enum dk_tcp_cls_status {
+    DK_TCP_CLS_OK = 0,
+    DK_TCP_CLS_E_ROW = 1,
+    DK_TCP_CLS_E_ORDER = 2,
+    DK_TCP_CLS_E_STATE = 3,
+    DK_TCP_CLS_E_BADF = 4,
+    DK_TCP_CLS_E_RX_STATE = 5,
+    DK_TCP_CLS_E_LINK = 6,
+    DK_TCP_CLS_E_WSCALE = 7,
+    DK_TCP_CLS_E_WINDOW = 8,
+    DK_TCP_CLS_E_SLOT = 9,
+    DK_TCP_CLS_NO_ROOM = 10
+};
+
+/* Outputs (device). Per batch frame, [n] (dk_tcp_close_process only): action, state_after, ack_action (one byte each),
+ * reply_frame. Per reply, [max_frames]: off_out, len_out (a dk_rx_batch over `out`), frame_seg (optional: the batch
+ * frame that triggered it). done: [max_done]. Per row, [nconns]: status (enum dk_tcp_cls_status), fin_frame
+ * (dk_tcp_close_process only). n_frames, n_done: one word each, the call's need. */
+typedef struct dk_tcp_cls_results {
+    uint8_t* action;
+    uint8_t* state_after;
+    uint8_t* ack_action;
+    uint32_t* reply_frame;
+    uint32_t* off_out;
+    uint16_t* len_out;
+    uint32_t* frame_seg;
+    dk_tcp_cls_done* done;
+    uint32_t* status;
+    uint32_t* fin_frame;
+    uint32_t* n_frames;
+    uint32_t* n_done;
+} dk_tcp_cls_results;
+
+/* close[0 .. nclose), status[nclose], push_conn / push_off / push_len [nclose] and the word n_markers are device
+ * arrays. Returns 0, EINVAL (a null required pointer, rows / rx_conns / tx_conns not 16-byte aligned, nclose >= 2^31:
+ * all before any GPU work), ENOMEM or EIO. nclose == 0 and nconns == 0 are valid calls that write n_markers = 0. */
+int dk_tcp_close_start(dk_tcp_closer* rows, dk_tcp_conn* rx_conns, const dk_tcp_tx_conn* tx_conns, uint32_t nconns,
+                       const uint32_t* close, uint32_t nclose, uint32_t* status, uint32_t* push_conn, uint32_t* push_off,
+                       uint32_t* push_len, uint32_t* n_markers, void* stream);
+
+/* rx = the results of the batch's dk_rx_process call (meta, flow_id, tcp_seq and tcp_ack are required), n its frames;
+ * dack and action_in optional. Returns 0, EINVAL (a null required pointer, a misaligned table, n >= 2^31, out_bytes >
+ * DK_RX_MAX_BLOB, nlinks == 0: all before any GPU work), ENOMEM or EIO. n == 0 and nconns == 0 are valid calls. */
+int dk_tcp_close_process(const dk_rx_results* rx, uint32_t n, dk_tcp_closer* rows, dk_tcp_conn* rx_conns,
+                         const dk_tcp_tx_conn* tx_conns, dk_tcp_dack_conn* dack, uint32_t nconns,
+                         const uint8_t* action_in, const dk_tx_link* links, uint32_t nlinks, uint64_t now_ns,
+                         uint8_t* out, uint64_t out_bytes, const dk_tcp_tx_layout* layout, uint32_t max_frames,
+                         uint32_t max_done, uint32_t flags, const dk_tcp_cls_results* results, void* stream);
+
+/* tx_conns optional. status: [nconns]. Returns 0, EINVAL (a null required pointer, a misaligned table), ENOMEM or EIO. */
+int dk_tcp_close_timers(dk_tcp_closer* rows, dk_tcp_tx_conn* tx_conns, uint32_t nconns, uint64_t now_ns,
+                        dk_tcp_cls_done* done, uint32_t max_done, uint32_t* n_done, uint32_t* status, void* stream);
 
 #ifdef __cplusplus
 }
