@@ -31,8 +31,10 @@ from .tcp_listen import ListenResults, ListenTable, listen_process, listen_relea
 from .tcp_connect import (ConnectResults, conn_of_flow, conn_rows_from_connect_ready, connect_process, connect_start,  # noqa: F401
                           connect_timers, connector_table)
 from .tcp_close import CloseResults, close_process, close_start, close_timers, closer_table  # noqa: F401
+from .arp import ArpResults, ArpTable, arp_cfg, arp_lookup, arp_process, arp_query_start, arp_timers, query_table  # noqa: F401
 
-__all__ = ["CloseResults", "close_process", "close_start", "close_timers", "closer_table",
+__all__ = ["ArpResults", "ArpTable", "arp_cfg", "arp_lookup", "arp_process", "arp_query_start", "arp_timers", "query_table",
+           "CloseResults", "close_process", "close_start", "close_timers", "closer_table",
            "ConnectResults", "conn_of_flow", "conn_rows_from_connect_ready", "connect_process", "connect_start",
            "connect_timers", "connector_table",
            "ListenResults", "ListenTable", "listen_process", "listen_release", "listen_timers", "listener_table",

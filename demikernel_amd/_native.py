@@ -500,6 +500,75 @@ TCP_CLOSE_FUNCTIONS = [
                                     c_void_p]),
 ]
 
+# include/dk_arp.h, the ARP peer (dk_arp_*)
+DK_ARP_NONE = 0xFFFFFFFF
+DK_ARP_NO_LINK = 0xFFFFFFFF
+DK_ARP_FRAME_BYTES = 42
+DK_ARP_DISABLED = 1
+DK_ARP_MAX_RETRIES = 65534
+ARP_ACTION_BITS = {"HIT": 1, "INSERTED": 2, "REPLY": 4, "LEARNED": 8, "DROPPED": 16}
+ARP_SLOT_STATES = ["FREE", "LIVE", "TOMBSTONE"]
+ARP_QUERY_STATES = ["IDLE", "WAITING", "RESOLVED", "FAILED"]
+ARP_STATUSES = ["OK", "E_ROW", "E_STATE", "E_LINK", "E_SLOT", "NO_ROOM"]
+ARP_CFG_DTYPE = np.dtype([("local_ip", "<u4"), ("local_mac", "u1", (6,)), ("reserved0", "<u2"), ("flags", "<u4"),
+                          ("retry_count", "<u4"), ("reserved1", "<u4"), ("cache_ttl_ns", "<u8"), ("request_timeout_ns", "<u8")])
+ARP_SLOT_DTYPE = np.dtype([("ip", "<u4"), ("state", "<u4"), ("mac", "u1", (6,)), ("reserved", "<u2"),
+                           ("expiration_ns", "<u8")])
+ARP_QUERY_DTYPE = np.dtype([("ip", "<u4"), ("link", "<u4"), ("tag", "<u4"), ("state", "<u2"), ("err", "<u2"),
+                            ("deadline_ns", "<u8"), ("mac", "u1", (6,)), ("sent", "<u2")])
+ARP_READY_DTYPE = np.dtype([("row", "<u4"), ("tag", "<u4"), ("ip", "<u4"), ("frame", "<u4"), ("mac", "u1", (6,)),
+                            ("err", "<u2")])
+assert (ARP_CFG_DTYPE.itemsize, ARP_SLOT_DTYPE.itemsize, ARP_QUERY_DTYPE.itemsize,
+        ARP_READY_DTYPE.itemsize) == (40, 24, 32, 24)
+ARP_RESULT_FIELDS = ["action", "reply_frame", "off_out", "len_out", "frame_seg", "ready", "status", "n_frames",
+                     "n_ready", "n_entries"]
+
+
+def _mirror_arp(dtype: np.dtype):
+    return [(k, c_uint8 * 6 if dtype.fields[k][0].shape == (6,) else _NP_C[dtype.fields[k][0].str]) for k in dtype.names]
+
+
+class DkArpCfg(ctypes.Structure):
+    _fields_ = _mirror_arp(ARP_CFG_DTYPE)
+
+
+class DkArpSlot(ctypes.Structure):
+    _fields_ = _mirror_arp(ARP_SLOT_DTYPE)
+
+
+class DkArpQuery(ctypes.Structure):
+    _fields_ = _mirror_arp(ARP_QUERY_DTYPE)
+
+
+class DkArpReady(ctypes.Structure):
+    _fields_ = _mirror_arp(ARP_READY_DTYPE)
+
+
+class DkArpResults(ctypes.Structure):
+    _fields_ = [(name, c_void_p) for name in ARP_RESULT_FIELDS]
+
+
+ARP_FUNCTIONS = [
+    ("dk_arp_home", c_uint32, [c_uint32, c_uint32]),
+    ("dk_arp_fits", c_int, [c_uint32, c_uint64]),
+    ("dk_arp_table_create", c_int, [c_int32, c_uint32, POINTER(DkArpCfg), POINTER(c_void_p)]),
+    ("dk_arp_table_destroy", None, [c_void_p]),
+    ("dk_arp_table_stats", c_int, [c_void_p, POINTER(c_uint32), POINTER(c_uint64)]),
+    ("dk_arp_table_read", c_int, [c_void_p, c_void_p]),
+    ("dk_arp_table_write", c_int, [c_void_p, c_void_p]),
+    ("dk_arp_table_insert", c_int, [c_void_p, c_void_p, c_void_p, c_uint32, c_uint64]),
+    ("dk_arp_process", c_int, [c_void_p, POINTER(DkRxBatch), POINTER(DkRxResults), c_uint32, c_void_p, c_uint32,
+                               c_void_p, c_uint32, c_uint64, c_void_p, c_uint64, POINTER(DkTcpTxLayout), c_uint32,
+                               c_uint32, POINTER(DkArpResults), c_void_p]),
+    ("dk_arp_query_start", c_int, [c_void_p, c_void_p, c_uint32, c_void_p, c_uint32, c_void_p, c_uint32, c_uint64,
+                                   c_void_p, c_uint64, POINTER(DkTcpTxLayout), c_uint32, c_uint32,
+                                   POINTER(DkArpResults), c_void_p]),
+    ("dk_arp_timers", c_int, [c_void_p, c_void_p, c_uint32, c_void_p, c_uint32, c_uint64, c_void_p, c_uint64,
+                              POINTER(DkTcpTxLayout), c_uint32, c_uint32, POINTER(DkArpResults), c_void_p]),
+    ("dk_arp_lookup", c_int, [c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_uint32, c_void_p, c_void_p,
+                              c_void_p]),
+]
+
 # include/dk_diag.h (diagnostics, not the receive ABI)
 # include/dk_demi.h: delivered frames as demi_sgarray_t (host-side, no GPU work)
 class DemiSgaseg(ctypes.Structure):
@@ -571,6 +640,10 @@ ALL_FUNCTIONS = (FUNCTIONS + RING_FUNCTIONS + TCP_FUNCTIONS + TCP_ACK_FUNCTIONS 
                  DIAG_FUNCTIONS +
                  DEMI_FUNCTIONS + COMM_FUNCTIONS)
 
+# include/dk_arp.h is a header of its own: its functions are bound beside the list above (tests/test_arp_abi.py checks
+# them against that header, as tests/test_abi.py checks ALL_FUNCTIONS against the others).
+BOUND_FUNCTIONS = ALL_FUNCTIONS + ARP_FUNCTIONS
+
 _lib = None
 
 
@@ -589,7 +662,7 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     except ImportError:
         pass
     lib = ctypes.CDLL(path)
-    for name, restype, argtypes in ALL_FUNCTIONS:
+    for name, restype, argtypes in BOUND_FUNCTIONS:
         fn = getattr(lib, name, None)
         if fn is None:
             if path != LIB_PATH:

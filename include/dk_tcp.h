@@ -1082,7 +1082,8 @@ int dk_tcp_listen_release(dk_tcp_listen_table* t, dk_tcp_listener* listeners, ui
  * as a context's calls are; asynchronous on the caller's stream; the environment is never read. These entry points are
  * additive: DK_RX_ABI_VERSION stays 4.
  * Out of scope: the ephemeral-port allocator and the socket table's Active entry (the host's, before
- * dk_tcp_connect_start) and its removal on failure; ARP resolution before the first SYN; building the rows of the five
+ * dk_tcp_connect_start) and its removal on failure; ARP resolution before the first SYN (include/dk_arp.h: a resolved dk_arp_query writes the
+ * destination MAC into links[], which dk_tcp_connect_start then takes unread by the host); building the rows of the five
  * TCP tables on the device; the closing states (the dk_tcp_close_* section); simultaneous open (the reference has none).
  * ------------------------------------------------------------------------------------------------------------- */
 #define DK_TCP_CON_NONE 0xFFFFFFFFu
