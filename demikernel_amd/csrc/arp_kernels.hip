@@ -26,14 +26,13 @@
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>
 
-#include <algorithm>
 #include <cerrno>
 #include <cstdint>
 #include <cstring>
 #include <vector>
 
 #include "../../include/dk_arp.h"
-#include "rx_common.h"
+#include "ctl_common.h"
 
 struct dk_arp_table {
     int device = 0;
@@ -41,17 +40,13 @@ struct dk_arp_table {
     dk_arp_cfg cfg{};
     dk_arp_slot* slots = nullptr;
     uint64_t* consumed = nullptr;  // one device word: never-used slots consumed
-    void* scratch = nullptr;
-    size_t scratch_cap = 0;
-    hipEvent_t last = nullptr;  // serialisation, as a context's
-    hipStream_t last_stream = nullptr;
-    bool used = false;
+    dk::ctl::CallScratch call;  // serialisation, as a context's; its event is made with the table
 };
 
 namespace dk_arp {
 namespace {
+using namespace dk::ctl;
 
-constexpr uint32_t kBlock = 256, kWave = 64;
 constexpr uint32_t kNone = DK_ARP_NONE;
 constexpr uint32_t kBusy = 3;  // a slot an insert of this launch has claimed and not yet published
 enum Tot : uint32_t { kFrames = 0, kReady = 1, kNew = 2, kRemoved = 3, kLive = 4, kTots = 5 };
@@ -122,12 +117,6 @@ __device__ __forceinline__ bool fits(const Params& P) {
            entries(P) <= P.cap / 2 && (P.tot[kFrames] == 0 || slot_room(P));
 }
 
-__device__ __forceinline__ void min32(uint32_t* p, uint32_t v) {
-    __hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void max32(uint32_t* p, uint32_t v) {
-    __hip_atomic_fetch_max(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 // One add per wave of the lanes that hold `pred`. Every lane of the wave calls it.
 __device__ __forceinline__ void count(uint64_t* p, bool pred) {
     const uint64_t b = __ballot(pred);
@@ -496,53 +485,6 @@ __global__ __launch_bounds__(kBlock) void arp_lookup_kernel(Params P, const uint
 }
 
 // ---- the host side --------------------------------------------------------------------------------------------------
-struct DeviceGuard {
-    int prev = -1;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) (void)hipSetDevice(dev);
-    }
-    ~DeviceGuard() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
-size_t round16(size_t b) { return (b + 15) & ~(size_t)15; }
-
-struct Carver {
-    uint8_t* b;
-    template <class T>
-    T* take(size_t count) {
-        T* p = reinterpret_cast<T*>(b);
-        b += round16(count * sizeof(T));
-        return p;
-    }
-};
-
-// The table's scratch grown to `need` bytes; waits for in-flight work on the old one first.
-int ensure_scratch(dk_arp_table* t, size_t need) {
-    if (t->scratch_cap >= need) return 0;
-    if (t->used && hipEventSynchronize(t->last) != hipSuccess) return EIO;
-    if (t->scratch) (void)hipFree(t->scratch);
-    t->scratch = nullptr, t->scratch_cap = 0;
-    if (hipMalloc(&t->scratch, need) != hipSuccess) return ENOMEM;
-    t->scratch_cap = need;
-    return 0;
-}
-int enter(dk_arp_table* t, hipStream_t s) {
-    if (t->used && t->last_stream != s && hipStreamWaitEvent(s, t->last, 0) != hipSuccess) return EIO;
-    return 0;
-}
-int leave(dk_arp_table* t, hipStream_t s) {
-    if (hipGetLastError() != hipSuccess) return EIO;
-    if (hipEventRecord(t->last, s) != hipSuccess) return EIO;
-    t->last_stream = s;
-    t->used = true;
-    return 0;
-}
-
-dim3 grid_for(uint32_t items) { return dim3((items + kBlock - 1) / kBlock); }
-
 // What dk_arp_process, dk_arp_query_start and dk_arp_timers check before any GPU work.
 bool bad_common(const dk_arp_table* t, const void* rows, uint32_t nrows, const dk_tx_link* links, uint32_t nlinks,
                 uint64_t out_bytes, const dk_tcp_tx_layout* layout, const dk_arp_results* res) {
@@ -607,7 +549,7 @@ int dk_arp_table_create(int32_t device, uint32_t cap, const dk_arp_cfg* cfg, dk_
     t->device = device, t->cap = cap, t->cfg = *cfg;
     if (hipMalloc(&t->slots, (size_t)cap * sizeof(dk_arp_slot)) != hipSuccess ||
         hipMalloc(&t->consumed, sizeof(uint64_t)) != hipSuccess ||
-        hipEventCreateWithFlags(&t->last, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&t->call.last, hipEventDisableTiming) != hipSuccess ||
         hipMemset(t->slots, 0, (size_t)cap * sizeof(dk_arp_slot)) != hipSuccess ||
         hipMemset(t->consumed, 0, sizeof(uint64_t)) != hipSuccess) {
         dk_arp_table_destroy(t);
@@ -619,21 +561,21 @@ int dk_arp_table_create(int32_t device, uint32_t cap, const dk_arp_cfg* cfg, dk_
 
 void dk_arp_table_destroy(dk_arp_table* t) {
     if (!t) return;
-    dk_arp::DeviceGuard g(t->device);
-    if (t->used) (void)hipEventSynchronize(t->last);
+    dk::ctl::DeviceGuard g(t->device);
+    if (t->call.used) (void)hipEventSynchronize(t->call.last);
     if (t->slots) (void)hipFree(t->slots);
     if (t->consumed) (void)hipFree(t->consumed);
-    if (t->scratch) (void)hipFree(t->scratch);
-    if (t->last) (void)hipEventDestroy(t->last);
+    if (t->call.scratch) (void)hipFree(t->call.scratch);
+    if (t->call.last) (void)hipEventDestroy(t->call.last);
     delete t;
 }
 
 int dk_arp_table_stats(dk_arp_table* t, uint32_t* cap, uint64_t* consumed) {
     if (!t) return EINVAL;
-    dk_arp::DeviceGuard g(t->device);
+    dk::ctl::DeviceGuard g(t->device);
     if (cap) *cap = t->cap;
     if (consumed) {
-        if (t->used && hipEventSynchronize(t->last) != hipSuccess) return EIO;
+        if (t->call.used && hipEventSynchronize(t->call.last) != hipSuccess) return EIO;
         if (hipMemcpy(consumed, t->consumed, sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess) return EIO;
     }
     return 0;
@@ -641,15 +583,15 @@ int dk_arp_table_stats(dk_arp_table* t, uint32_t* cap, uint64_t* consumed) {
 
 int dk_arp_table_read(dk_arp_table* t, dk_arp_slot* rows) {
     if (!t || !rows) return EINVAL;
-    dk_arp::DeviceGuard g(t->device);
-    if (t->used && hipEventSynchronize(t->last) != hipSuccess) return EIO;
+    dk::ctl::DeviceGuard g(t->device);
+    if (t->call.used && hipEventSynchronize(t->call.last) != hipSuccess) return EIO;
     return hipMemcpy(rows, t->slots, (size_t)t->cap * sizeof(dk_arp_slot), hipMemcpyDeviceToHost) == hipSuccess ? 0 : EIO;
 }
 
 int dk_arp_table_write(dk_arp_table* t, const dk_arp_slot* rows) {
     if (!t || !rows) return EINVAL;
-    dk_arp::DeviceGuard g(t->device);
-    if (t->used && hipEventSynchronize(t->last) != hipSuccess) return EIO;
+    dk::ctl::DeviceGuard g(t->device);
+    if (t->call.used && hipEventSynchronize(t->call.last) != hipSuccess) return EIO;
     uint64_t consumed = 0;
     for (uint32_t s = 0; s < t->cap; s++) {
         if (rows[s].state > DK_ARP_SLOT_TOMBSTONE) return EINVAL;
@@ -702,13 +644,13 @@ int dk_arp_process(dk_arp_table* t, const dk_rx_batch* batch, const dk_rx_result
     const size_t need = ff_bytes + zero_bytes + round16((size_t)hcap * 4) + round16(hcap) + round16((size_t)n * 4) +
                         round16(n) + round16((size_t)n * 8) + round16((size_t)sb * 8) + 3 * round16((size_t)nrows * 4) +
                         round16(sort_bytes) + 16;
-    if (int rc = ensure_scratch(t, need)) return rc;
-    if (int rc = enter(t, s)) return rc;
+    if (int rc = t->call.grow(need)) return rc;
+    if (int rc = t->call.order(s)) return rc;
     Params P{};
     fill_common(P, t, rows, nrows, links, nlinks, out, out_bytes, layout, max_frames, max_ready, res);
     P.frames = batch->frames, P.frames_bytes = batch->frames_bytes, P.off = batch->off;
     P.meta = rx->meta, P.src = rx->src_ip, P.dst = rx->dst_ip, P.n = n, P.clock = clock_ns, P.hcap = hcap;
-    Carver c{static_cast<uint8_t*>(t->scratch)};
+    Carver c{static_cast<uint8_t*>(t->call.scratch)};
     P.hL = c.take<uint32_t>(hcap);
     P.hfirst = c.take<uint32_t>(hcap);
     P.hts = c.take<uint32_t>(hcap);
@@ -751,7 +693,7 @@ int dk_arp_process(dk_arp_table* t, const dk_rx_batch* batch, const dk_rx_result
         if (nrows) hipLaunchKernelGGL(arp_wake_kernel, grid_for(nrows), dim3(kBlock), 0, s, P);
     }
     hipLaunchKernelGGL(arp_finish_kernel, dim3(1), dim3(kBlock), 0, s, P, (uint32_t)kProcess);
-    return leave(t, s);
+    return t->call.record(s);
 }
 
 int dk_arp_query_start(dk_arp_table* t, dk_arp_query* rows, uint32_t nrows, const uint32_t* start, uint32_t nstart,
@@ -767,12 +709,12 @@ int dk_arp_query_start(dk_arp_table* t, dk_arp_query* rows, uint32_t nrows, cons
     const size_t ff_bytes = round16((size_t)nrows * 4) + 16, zero_bytes = round16(kTots * 8);
     const size_t need = ff_bytes + zero_bytes + round16(t->cap) + round16((size_t)nstart * 4) + round16(nstart) +
                         2 * round16((size_t)nstart * 8) + round16((size_t)sb * 8) + 16;
-    if (int rc = ensure_scratch(t, need)) return rc;
-    if (int rc = enter(t, s)) return rc;
+    if (int rc = t->call.grow(need)) return rc;
+    if (int rc = t->call.order(s)) return rc;
     Params P{};
     fill_common(P, t, rows, nrows, links, nlinks, out, out_bytes, layout, max_frames, max_ready, res);
     P.start = start, P.nstart = nstart, P.now = now_ns;
-    Carver c{static_cast<uint8_t*>(t->scratch)};
+    Carver c{static_cast<uint8_t*>(t->call.scratch)};
     P.term = c.take<uint32_t>(nrows);
     P.f0 = c.take<uint32_t>(1);
     P.tot = c.take<uint64_t>(kTots);
@@ -794,8 +736,8 @@ int dk_arp_query_start(dk_arp_table* t, dk_arp_query* rows, uint32_t nrows, cons
             return EIO;
         hipLaunchKernelGGL(arp_open_kernel, grid_for(nstart), dim3(kBlock), 0, s, P);
     }
-    hipLaunchKernelGGL(arp_finish_kernel, grid_for(std::max(nstart, 1u)), dim3(kBlock), 0, s, P, (uint32_t)kStart);
-    return leave(t, s);
+    hipLaunchKernelGGL(arp_finish_kernel, grid_for(nstart), dim3(kBlock), 0, s, P, (uint32_t)kStart);
+    return t->call.record(s);
 }
 
 int dk_arp_timers(dk_arp_table* t, dk_arp_query* rows, uint32_t nrows, dk_tx_link* links, uint32_t nlinks,
@@ -810,12 +752,12 @@ int dk_arp_timers(dk_arp_table* t, dk_arp_query* rows, uint32_t nrows, dk_tx_lin
     const size_t zero_bytes = round16(kTots * 8);
     const size_t need = 16 + zero_bytes + round16(t->cap) + round16((size_t)nrows * 4) + round16(nrows) +
                         2 * round16((size_t)nrows * 8) + round16((size_t)sb * 8) + 16;
-    if (int rc = ensure_scratch(t, need)) return rc;
-    if (int rc = enter(t, s)) return rc;
+    if (int rc = t->call.grow(need)) return rc;
+    if (int rc = t->call.order(s)) return rc;
     Params P{};
     fill_common(P, t, rows, nrows, links, nlinks, out, out_bytes, layout, max_frames, max_ready, res);
     P.now = now_ns;
-    Carver c{static_cast<uint8_t*>(t->scratch)};
+    Carver c{static_cast<uint8_t*>(t->call.scratch)};
     P.f0 = c.take<uint32_t>(1);
     P.tot = c.take<uint64_t>(kTots);
     P.keep = c.take<uint8_t>(t->cap);
@@ -835,7 +777,7 @@ int dk_arp_timers(dk_arp_table* t, dk_arp_query* rows, uint32_t nrows, dk_tx_lin
         hipLaunchKernelGGL(arp_expire_kernel, grid_for(nrows), dim3(kBlock), 0, s, P);
     }
     hipLaunchKernelGGL(arp_finish_kernel, dim3(1), dim3(kBlock), 0, s, P, (uint32_t)kTimers);
-    return leave(t, s);
+    return t->call.record(s);
 }
 
 int dk_arp_lookup(dk_arp_table* t, const uint32_t* ips, const uint32_t* link, uint32_t n, dk_tx_link* links,
@@ -845,11 +787,11 @@ int dk_arp_lookup(dk_arp_table* t, const uint32_t* ips, const uint32_t* link, ui
     if (n && (!ips || !macs_out || !found)) return EINVAL;
     DeviceGuard g(t->device);
     const hipStream_t s = (hipStream_t)stream;
-    if (int rc = enter(t, s)) return rc;
+    if (int rc = t->call.order(s)) return rc;
     Params P{};
     P.slots = t->slots, P.cap = t->cap, P.cfg = t->cfg, P.links = links, P.nlinks = nlinks, P.n = n;
     if (n) hipLaunchKernelGGL(arp_lookup_kernel, grid_for(n), dim3(kBlock), 0, s, P, ips, link, macs_out, found);
-    return leave(t, s);
+    return t->call.record(s);
 }
 
 }  // extern "C"

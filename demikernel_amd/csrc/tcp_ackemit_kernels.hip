@@ -32,7 +32,7 @@
 
 #include "../../include/dk_diag.h"
 #include "../../include/dk_tcp.h"
-#include "rx_common.h"
+#include "ctl_common.h"
 #include "tcp_order.h"
 
 namespace dk_tcp_ackemit {
@@ -378,7 +378,7 @@ struct DeviceGuard {
     }
 };
 
-size_t round16(size_t b) { return (b + 15) & ~(size_t)15; }
+using dk::ctl::round16;
 
 }  // namespace
 }  // namespace dk_tcp_ackemit

@@ -18,31 +18,24 @@
 //                           words and NO_ROOM.
 // dk_tcp_close_start is a prefix maximum (one workgroup), flag, scan, build over close[] entries; dk_tcp_close_timers is
 // flag, scan, build over rows. No loop depends on another workgroup's progress. Atomics are agent-scope integer
-// __hip_atomic_* on global memory; everything else is plain vector stores.
-// The frame builder is a copy of tcp_connect_kernels.hip's without the SYN options: that file is untouched.
+// __hip_atomic_* on global memory; everything else is plain vector stores. The frame builder is ctl_common.h's.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <cerrno>
 #include <cstdint>
 #include <mutex>
 
 #include "../../include/dk_tcp.h"
-#include "rx_common.h"
+#include "ctl_common.h"
 
 namespace dk_tcp_close {
 namespace {
+using namespace dk::ctl;
 
-constexpr uint32_t kBlock = 256, kWave = 64;
 constexpr uint32_t kNone = DK_TCP_CLS_NONE;
-constexpr int kMaxDevices = 64;
 
 // bits[i]: what the classify pass leaves per frame
 constexpr uint32_t kA = 1, kU = 2, kF = 4, kLive = 8;
-
-__device__ __forceinline__ void min32(uint32_t* p, uint32_t v) {
-    __hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 
 struct Params {
     dk_rx_results rx;
@@ -122,53 +115,11 @@ __device__ __forceinline__ RowEnd row_end(const Params& P, uint32_t c) {
     return e;
 }
 
-// ---- the 54-byte ACK ----------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t be16s(uint32_t x) { return (x >> 16) + (x & 0xFFFFu); }
-__device__ __forceinline__ uint32_t bsw16(uint32_t x) { return ((x & 0xFFu) << 8) | ((x >> 8) & 0xFFu); }
-__device__ __forceinline__ uint32_t ipbe(uint32_t a) { return bsw16(a & 0xFFFFu) + bsw16(a >> 16); }
-__device__ __forceinline__ uint32_t csum_fold(uint32_t s) {
-    s = (s >> 16) + (s & 0xFFFFu);
-    s = (s >> 16) + (s & 0xFFFFu);
-    return ~s & 0xFFFFu;
-}
-
 // Ethernet2 + IPv4 + TCP, flags ACK, no options, no payload: the bytes dk_tcp_ack_emit writes for the connection.
 __device__ void build_ack(uint8_t* a, const dk_tx_link* lk, const dk_tcp_tx_conn& T, uint32_t ack, uint32_t win,
                           bool offload) {
-    const uint32_t* lw = reinterpret_cast<const uint32_t*>(lk);
-    const uint32_t ipw = T.ip_word, src = T.local_ip, dst = T.remote_ip, seq = T.snd_nxt;
-    const uint32_t sport = T.ports & 0xFFFFu, dport = T.ports >> 16;
-    const uint32_t tot = 40u, b12 = 5u << 4, b13 = 0x10u;
-    const uint32_t ident = ipw & 0xFFFFu, ttl = (ipw >> 16) & 0xFFu, tos = ipw >> 24;
-    const uint32_t ipc = csum_fold((0x4500u | tos) + tot + ident + 0x4000u + ((ttl << 8) | 6u) + ipbe(src) + ipbe(dst));
-    uint32_t c = 0;
-    if (!offload)
-        c = csum_fold(ipbe(src) + ipbe(dst) + 6u + 20u + sport + dport + be16s(seq) + be16s(ack) + ((b12 << 8) | b13) + win);
-    uint32_t d[14];
-    d[0] = lw[0];
-    d[1] = lw[1];
-    d[2] = lw[2];
-    d[3] = 0x0008u | 0x45u << 16 | tos << 24;
-    d[4] = bsw16(tot) | bsw16(ident) << 16;
-    d[5] = 0x0040u | ttl << 16 | 6u << 24;
-    d[6] = bsw16(ipc) | (src & 0xFFFFu) << 16;
-    d[7] = (src >> 16) | (dst & 0xFFFFu) << 16;
-    d[8] = (dst >> 16) | bsw16(sport) << 16;
-    const uint32_t sq = __builtin_bswap32(seq), ak = __builtin_bswap32(ack);
-    d[9] = bsw16(dport) | sq << 16;
-    d[10] = (sq >> 16) | ak << 16;
-    d[11] = (ak >> 16) | b12 << 16 | b13 << 24;
-    d[12] = bsw16(win) | bsw16(c) << 16;
-    d[13] = 0;  // urgent pointer
-    if ((reinterpret_cast<uintptr_t>(a) & 3u) == 0) {
-        uint32_t* q = reinterpret_cast<uint32_t*>(a);
-#pragma unroll
-        for (int k = 0; k < 13; k++) q[k] = d[k];
-        *reinterpret_cast<uint16_t*>(a + 52) = (uint16_t)d[13];
-    } else {
-#pragma unroll
-        for (int k = 0; k < (int)DK_TCP_CLS_ACK_BYTES; k++) a[k] = (uint8_t)(d[k >> 2] >> ((k & 3) * 8));
-    }
+    tcp_frame(a, lk, T.ip_word, T.local_ip, T.remote_ip, T.ports & 0xFFFFu, T.ports >> 16, T.snd_nxt, ack, 0x10u, win, false,
+              0u, 0u, offload);
 }
 
 // Reply f of the call: an ACK of connection c carrying RCV.NXT = ack, triggered by batch frame seg.
@@ -447,54 +398,8 @@ __global__ __launch_bounds__(kBlock) void cls_open_kernel(Params P) {
 }
 
 // ---- the host side ------------------------------------------------------------------------------------------------------
-struct DevicePool {  // one per device: the calls' scratch, and the event that serialises them on it
-    void* scratch = nullptr;
-    size_t cap = 0;
-    hipEvent_t last = nullptr;
-    hipStream_t last_stream = nullptr;
-    bool used = false;
-};
-DevicePool g_pool[kMaxDevices];
+CallScratch g_pool[kMaxDevices];  // one per device: the calls' scratch, and the event that serialises them on it
 std::mutex g_mutex;
-
-size_t round16(size_t b) { return (b + 15) & ~(size_t)15; }
-
-struct Carver {
-    uint8_t* b;
-    template <class T>
-    T* take(size_t count) {
-        T* p = reinterpret_cast<T*>(b);
-        b += round16(count * sizeof(T));
-        return p;
-    }
-};
-
-dim3 grid_for(uint32_t items) { return dim3((std::max(items, 1u) + kBlock - 1) / kBlock); }
-
-// The current device's pool with at least `need` bytes, the caller's stream ordered behind the pool's last call.
-int enter(size_t need, hipStream_t s, DevicePool** out) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) return EIO;
-    DevicePool* p = &g_pool[dev];
-    if (!p->last && hipEventCreateWithFlags(&p->last, hipEventDisableTiming) != hipSuccess) return EIO;
-    if (p->cap < need) {
-        if (p->used && hipEventSynchronize(p->last) != hipSuccess) return EIO;  // in-flight work on the old one
-        if (p->scratch) (void)hipFree(p->scratch);
-        p->scratch = nullptr, p->cap = 0;
-        if (hipMalloc(&p->scratch, need) != hipSuccess) return ENOMEM;
-        p->cap = need;
-    }
-    if (p->used && p->last_stream != s && hipStreamWaitEvent(s, p->last, 0) != hipSuccess) return EIO;
-    *out = p;
-    return 0;
-}
-int leave(DevicePool* p, hipStream_t s) {
-    if (hipGetLastError() != hipSuccess) return EIO;
-    if (hipEventRecord(p->last, s) != hipSuccess) return EIO;
-    p->last_stream = s;
-    p->used = true;
-    return 0;
-}
 
 bool misaligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
 
@@ -515,8 +420,8 @@ int dk_tcp_close_start(dk_tcp_closer* rows, dk_tcp_conn* rx_conns, const dk_tcp_
     const hipStream_t s = (hipStream_t)stream;
     const uint32_t sb = dk_tcp_tx_scan_tiles(nclose);
     const size_t need = round16(2 * 8) + 2 * round16((size_t)nclose * 8) + round16((size_t)sb * 8) + 16;
-    DevicePool* pool = nullptr;
-    if (int rc = enter(need, s, &pool)) return rc;
+    CallScratch* pool = nullptr;
+    if (int rc = enter_pool(g_pool, need, s, &pool)) return rc;
     Params P{};
     P.rows = rows, P.rxc = rx_conns, P.txc = tx_conns, P.nconns = nconns;
     P.close = close, P.nclose = nclose, P.st_status = status;
@@ -534,7 +439,7 @@ int dk_tcp_close_start(dk_tcp_closer* rows, dk_tcp_conn* rx_conns, const dk_tcp_
         if (dk_tcp_tx_scan(P.flag_r, nclose, bsum, P.tot, s)) return EIO;
     }
     hipLaunchKernelGGL(cls_open_kernel, grid_for(nclose), dim3(kBlock), 0, s, P);
-    return leave(pool, s);
+    return pool->record(s);
 }
 
 int dk_tcp_close_process(const dk_rx_results* rx, uint32_t n, dk_tcp_closer* rows, dk_tcp_conn* rx_conns,
@@ -558,8 +463,8 @@ int dk_tcp_close_process(const dk_rx_results* rx, uint32_t n, dk_tcp_closer* row
     const size_t zero_bytes = 2 * round16((size_t)nconns * 4) + round16(2 * 8);
     const size_t need = ff_bytes + zero_bytes + 2 * round16((size_t)nconns * 4) + 3 * round16(n) +
                         2 * round16((size_t)n * 8) + round16((size_t)sb * 8) + 16;
-    DevicePool* pool = nullptr;
-    if (int rc = enter(need, s, &pool)) return rc;
+    CallScratch* pool = nullptr;
+    if (int rc = enter_pool(g_pool, need, s, &pool)) return rc;
     Params P{};
     P.rx = *rx, P.n = n, P.rows = rows, P.rxc = rx_conns, P.txc = tx_conns, P.dack = dack, P.nconns = nconns;
     P.action_in = action_in, P.links = links, P.nlinks = nlinks, P.now = now_ns;
@@ -593,7 +498,7 @@ int dk_tcp_close_process(const dk_rx_results* rx, uint32_t n, dk_tcp_closer* row
         hipLaunchKernelGGL(cls_build_kernel, grid_for(n), dim3(kBlock), 0, s, P);
     }
     hipLaunchKernelGGL(cls_finish_kernel, grid_for(nconns), dim3(kBlock), 0, s, P);
-    return leave(pool, s);
+    return pool->record(s);
 }
 
 int dk_tcp_close_timers(dk_tcp_closer* rows, dk_tcp_tx_conn* tx_conns, uint32_t nconns, uint64_t now_ns,
@@ -606,8 +511,8 @@ int dk_tcp_close_timers(dk_tcp_closer* rows, dk_tcp_tx_conn* tx_conns, uint32_t 
     const uint32_t sb = dk_tcp_tx_scan_tiles(nconns);
     const size_t need = round16(2 * 8) + round16((size_t)nconns * 4) + round16((size_t)nconns * 8) +
                         round16((size_t)sb * 8) + 16;
-    DevicePool* pool = nullptr;
-    if (int rc = enter(need, s, &pool)) return rc;
+    CallScratch* pool = nullptr;
+    if (int rc = enter_pool(g_pool, need, s, &pool)) return rc;
     Params P{};
     P.rows = rows, P.txw = tx_conns, P.nconns = nconns, P.now = now_ns, P.max_done = max_done;
     P.res.done = done, P.res.n_done = n_done, P.st_status = status;
@@ -623,7 +528,7 @@ int dk_tcp_close_timers(dk_tcp_closer* rows, dk_tcp_tx_conn* tx_conns, uint32_t 
         if (dk_tcp_tx_scan(P.flag_y, nconns, bsum, P.tot + 1, s)) return EIO;
     }
     hipLaunchKernelGGL(cls_expire_kernel, grid_for(nconns), dim3(kBlock), 0, s, P);
-    return leave(pool, s);
+    return pool->record(s);
 }
 
 }  // extern "C"

@@ -27,36 +27,26 @@
 //                            test, made on the device; con_finish_kernel the two words and NO_ROOM.
 // dk_tcp_connect_start and dk_tcp_connect_timers are the same three stages (flag, scan, build) over start[] entries and
 // rows. No loop depends on another workgroup's progress. Atomics are agent-scope integer __hip_atomic_* on global
-// memory; everything else is plain vector stores.
-// The CRC routine and the frame builder are copies of tcp_listen_kernels.hip's: that file is untouched.
+// memory; everything else is plain vector stores. The ISN's CRC and the frame builder are ctl_common.h's.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <cerrno>
 #include <cstdint>
 #include <mutex>
 
 #include "../../include/dk_tcp.h"
-#include "rx_common.h"
+#include "ctl_common.h"
 
 namespace dk_tcp_connect {
 namespace {
+using namespace dk::ctl;
 
-constexpr uint32_t kBlock = 256, kWave = 64;
 constexpr uint32_t kNone = DK_TCP_CON_NONE;
-constexpr int kMaxDevices = 64;
 
 // What the classify pass leaves per frame: kind | process_ack's verdict << 4.
 enum Kind : uint32_t { kSkip = 0, kForward = 1, kOrphaned = 2, kConn = 3 };
 enum Verdict : uint32_t { kEagain = 0, kRefused = 1, kAccepted = 2 };
 constexpr uint32_t kDecides = 0x80u;  // act[]: this frame writes its row
-
-__device__ __forceinline__ void min32(uint32_t* p, uint32_t v) {
-    __hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ uint32_t add32(uint32_t* p, uint32_t v) {
-    return __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 
 struct Params {
     dk_rx_results rx;
@@ -90,77 +80,6 @@ __device__ __forceinline__ bool fits(const Params& P) {
     return dk::tcp_tx_fits(P.tot[0], P.max_frames, P.stride, P.out_bytes) && P.tot[1] <= P.max_ready;
 }
 
-// CRC-32/CKSUM of the 16 bytes isn_generator.rs feeds it (ips in octet order: their first octet is the low byte).
-__device__ uint32_t isn_crc(uint32_t rip, uint32_t rport, uint32_t lip, uint32_t lport, uint32_t nonce) {
-    const uint32_t w[4] = {__builtin_bswap32(rip), (rport & 0xFFFFu) << 16 | (__builtin_bswap32(lip) >> 16),
-                           (__builtin_bswap32(lip) << 16) | (lport & 0xFFFFu), nonce};
-    uint32_t crc = 0;
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        crc ^= w[k];  // four message bytes, most significant first
-        for (int b = 0; b < 32; b++) crc = (crc << 1) ^ ((crc >> 31) ? 0x04C11DB7u : 0u);
-    }
-    return ~crc;
-}
-
-__device__ __forceinline__ uint32_t be16s(uint32_t x) { return (x >> 16) + (x & 0xFFFFu); }
-__device__ __forceinline__ uint32_t bsw16(uint32_t x) { return ((x & 0xFFu) << 8) | ((x >> 8) & 0xFFu); }
-__device__ __forceinline__ uint32_t ipbe(uint32_t a) { return bsw16(a & 0xFFFFu) + bsw16(a >> 16); }
-__device__ __forceinline__ uint32_t csum_fold(uint32_t s) {
-    s = (s >> 16) + (s & 0xFFFFu);
-    s = (s >> 16) + (s & 0xFFFFu);
-    return ~s & 0xFFFFu;
-}
-
-// One frame at a: Ethernet2 + IPv4 + TCP with no payload, the bytes dk_tx_serialize writes for the descriptor.
-// syn: options [MSS(mss), WindowScale(ws)], 62 bytes; else 54.
-__device__ void build_frame(uint8_t* a, const dk_tx_link* lk, uint32_t ipw, uint32_t src, uint32_t dst, uint32_t sport,
-                            uint32_t dport, uint32_t seq, uint32_t ack, uint32_t b13, uint32_t win, bool syn, uint32_t mss,
-                            uint32_t ws, bool offload) {
-    const uint32_t* lw = reinterpret_cast<const uint32_t*>(lk);
-    const uint32_t hl = syn ? 28u : 20u, tot = 20u + hl;
-    const uint32_t ident = ipw & 0xFFFFu, ttl = (ipw >> 16) & 0xFFu, tos = ipw >> 24;
-    const uint32_t ipc = csum_fold((0x4500u | tos) + tot + ident + 0x4000u + ((ttl << 8) | 6u) + ipbe(src) + ipbe(dst));
-    const uint32_t b12 = (hl / 4) << 4;
-    uint32_t c = 0;
-    if (!offload) {
-        uint32_t s = ipbe(src) + ipbe(dst) + 6u + hl + sport + dport + be16s(seq) + be16s(ack) + ((b12 << 8) | b13) + win;
-        if (syn) s += 0x0204u + (mss & 0xFFFFu) + 0x0303u + ((ws & 0xFFu) << 8);
-        c = csum_fold(s);
-    }
-    uint32_t d[16];
-    d[0] = lw[0];
-    d[1] = lw[1];
-    d[2] = lw[2];
-    d[3] = 0x0008u | 0x45u << 16 | tos << 24;
-    d[4] = bsw16(tot) | bsw16(ident) << 16;
-    d[5] = 0x0040u | ttl << 16 | 6u << 24;
-    d[6] = bsw16(ipc) | (src & 0xFFFFu) << 16;
-    d[7] = (src >> 16) | (dst & 0xFFFFu) << 16;
-    d[8] = (dst >> 16) | bsw16(sport) << 16;
-    const uint32_t sq = __builtin_bswap32(seq), ak = __builtin_bswap32(ack);
-    d[9] = bsw16(dport) | sq << 16;
-    d[10] = (sq >> 16) | ak << 16;
-    d[11] = (ak >> 16) | b12 << 16 | b13 << 24;
-    d[12] = bsw16(win) | bsw16(c) << 16;
-    d[13] = syn ? 0x0402u << 16 : 0u;              // urgent pointer 0; kind 2, length 4
-    d[14] = bsw16(mss & 0xFFFFu) | 0x0303u << 16;  // the MSS; kind 3, length 3
-    d[15] = ws & 0xFFu;                            // the shift; EndOfOptionsList
-    const uint32_t nb = syn ? DK_TCP_CON_SYN_BYTES : DK_TCP_CON_ACK_BYTES;
-    if ((reinterpret_cast<uintptr_t>(a) & 3u) == 0) {
-        uint32_t* q = reinterpret_cast<uint32_t*>(a);
-#pragma unroll
-        for (int k = 0; k < 15; k++)
-            if ((uint32_t)(4 * k + 4) <= nb) q[k] = d[k];
-        if (syn) *reinterpret_cast<uint16_t*>(a + 60) = (uint16_t)d[15];
-        else *reinterpret_cast<uint16_t*>(a + 52) = (uint16_t)d[13];
-    } else {
-#pragma unroll
-        for (int k = 0; k < 62; k++)
-            if ((uint32_t)k < nb) a[k] = (uint8_t)(d[k >> 2] >> ((k & 3) * 8));
-    }
-}
-
 // The row checks that every call makes, in dk_tcp.h's order.
 __device__ __forceinline__ uint32_t row_check(const Params& P, const dk_tcp_connector& R) {
     if (R.window_scale > 14) return DK_TCP_CON_E_WSCALE;
@@ -176,9 +95,9 @@ __device__ void emit_frame(const Params& P, uint64_t f, uint32_t seg, const dk_t
     P.res.off_out[f] = foff;
     P.res.len_out[f] = (uint16_t)(syn ? DK_TCP_CON_SYN_BYTES : DK_TCP_CON_ACK_BYTES);
     if (P.res.frame_seg) P.res.frame_seg[f] = seg;
-    build_frame(P.out + foff, P.links + lk, R.ip_word, R.local_ip, R.remote_ip, R.local_port, R.remote_port,
-                syn ? R.local_isn : R.local_isn + 1u, ack, syn ? 0x02u : 0x10u, R.receive_window_size, syn,
-                R.advertised_mss, R.window_scale, (P.flags & DK_TX_OFFLOAD_TCP) != 0);
+    tcp_frame(P.out + foff, P.links + lk, R.ip_word, R.local_ip, R.remote_ip, R.local_port, R.remote_port,
+              syn ? R.local_isn : R.local_isn + 1u, ack, syn ? 0x02u : 0x10u, R.receive_window_size, syn, R.advertised_mss,
+              R.window_scale, (P.flags & DK_TX_OFFLOAD_TCP) != 0);
 }
 
 __device__ void error_record(dk_tcp_con_ready* Y, uint32_t r, uint32_t cause, uint32_t frame, uint32_t local_isn) {
@@ -487,54 +406,8 @@ __global__ __launch_bounds__(kBlock) void con_open_kernel(Params P) {
 }
 
 // ---- the host side ------------------------------------------------------------------------------------------------------
-struct DevicePool {  // one per device: the calls' scratch, and the event that serialises them on it
-    void* scratch = nullptr;
-    size_t cap = 0;
-    hipEvent_t last = nullptr;
-    hipStream_t last_stream = nullptr;
-    bool used = false;
-};
-DevicePool g_pool[kMaxDevices];
+CallScratch g_pool[kMaxDevices];  // one per device: the calls' scratch, and the event that serialises them on it
 std::mutex g_mutex;
-
-size_t round16(size_t b) { return (b + 15) & ~(size_t)15; }
-
-struct Carver {
-    uint8_t* b;
-    template <class T>
-    T* take(size_t count) {
-        T* p = reinterpret_cast<T*>(b);
-        b += round16(count * sizeof(T));
-        return p;
-    }
-};
-
-dim3 grid_for(uint32_t items) { return dim3((std::max(items, 1u) + kBlock - 1) / kBlock); }
-
-// The current device's pool with at least `need` bytes, the caller's stream ordered behind the pool's last call.
-int enter(size_t need, hipStream_t s, DevicePool** out) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) return EIO;
-    DevicePool* p = &g_pool[dev];
-    if (!p->last && hipEventCreateWithFlags(&p->last, hipEventDisableTiming) != hipSuccess) return EIO;
-    if (p->cap < need) {
-        if (p->used && hipEventSynchronize(p->last) != hipSuccess) return EIO;  // in-flight work on the old one
-        if (p->scratch) (void)hipFree(p->scratch);
-        p->scratch = nullptr, p->cap = 0;
-        if (hipMalloc(&p->scratch, need) != hipSuccess) return ENOMEM;
-        p->cap = need;
-    }
-    if (p->used && p->last_stream != s && hipStreamWaitEvent(s, p->last, 0) != hipSuccess) return EIO;
-    *out = p;
-    return 0;
-}
-int leave(DevicePool* p, hipStream_t s) {
-    if (hipGetLastError() != hipSuccess) return EIO;
-    if (hipEventRecord(p->last, s) != hipSuccess) return EIO;
-    p->last_stream = s;
-    p->used = true;
-    return 0;
-}
 
 // What every call checks before any GPU work.
 bool bad_common(const void* rows, uint32_t nrows, const dk_tx_link* links, uint32_t nlinks, uint64_t out_bytes,
@@ -574,8 +447,8 @@ int dk_tcp_connect_start(dk_tcp_connector* rows, uint32_t nrows, const uint32_t*
     const uint32_t sb = dk_tcp_tx_scan_tiles(nstart);
     const size_t ff_bytes = round16((size_t)nrows * 4), zero_bytes = round16(3 * 8);
     const size_t need = ff_bytes + zero_bytes + 2 * round16((size_t)nstart * 8) + round16((size_t)sb * 8) + 16;
-    DevicePool* pool = nullptr;
-    if (int rc = enter(need, s, &pool)) return rc;
+    CallScratch* pool = nullptr;
+    if (int rc = enter_pool(g_pool, need, s, &pool)) return rc;
     Params P{};
     fill_common(P, rows, nrows, links, nlinks, now_ns, out, out_bytes, layout, max_frames, max_ready, flags, res);
     P.start = start, P.nstart = nstart, P.gen = isn_gen;
@@ -597,7 +470,7 @@ int dk_tcp_connect_start(dk_tcp_connector* rows, uint32_t nrows, const uint32_t*
         hipLaunchKernelGGL(con_open_kernel, grid_for(nstart), dim3(kBlock), 0, s, P);
     }
     hipLaunchKernelGGL(con_finish_kernel, grid_for(nstart), dim3(kBlock), 0, s, P, nstart);
-    return leave(pool, s);
+    return pool->record(s);
 }
 
 int dk_tcp_connect_process(const dk_rx_results* rx, uint32_t n, dk_tcp_connector* rows, uint32_t nrows,
@@ -619,8 +492,8 @@ int dk_tcp_connect_process(const dk_rx_results* rx, uint32_t n, dk_tcp_connector
     const size_t zero_bytes = 3 * round16((size_t)nrows * 4) + round16(3 * 8);
     const size_t need = ff_bytes + zero_bytes + 7 * round16((size_t)n * 4) + 2 * round16(n) + 3 * round16((size_t)n * 8) +
                         round16((size_t)sb * 8) + 16;
-    DevicePool* pool = nullptr;
-    if (int rc = enter(need, s, &pool)) return rc;
+    CallScratch* pool = nullptr;
+    if (int rc = enter_pool(g_pool, need, s, &pool)) return rc;
     Params P{};
     fill_common(P, rows, nrows, links, nlinks, now_ns, out, out_bytes, layout, max_frames, max_ready, flags, res);
     P.rx = *rx, P.n = n, P.conn_of_flow = conn_of_flow, P.nflows = nflows, P.link = link;
@@ -670,7 +543,7 @@ int dk_tcp_connect_process(const dk_rx_results* rx, uint32_t n, dk_tcp_connector
             return EIO;
     }
     hipLaunchKernelGGL(con_finish_kernel, grid_for(nrows), dim3(kBlock), 0, s, P, nrows);
-    return leave(pool, s);
+    return pool->record(s);
 }
 
 int dk_tcp_connect_timers(dk_tcp_connector* rows, uint32_t nrows, const dk_tx_link* links, uint32_t nlinks,
@@ -685,8 +558,8 @@ int dk_tcp_connect_timers(dk_tcp_connector* rows, uint32_t nrows, const dk_tx_li
     const uint32_t sb = dk_tcp_tx_scan_tiles(nrows);
     const size_t zero_bytes = round16(3 * 8);
     const size_t need = zero_bytes + round16((size_t)nrows * 4) + 2 * round16((size_t)nrows * 8) + round16((size_t)sb * 8) + 16;
-    DevicePool* pool = nullptr;
-    if (int rc = enter(need, s, &pool)) return rc;
+    CallScratch* pool = nullptr;
+    if (int rc = enter_pool(g_pool, need, s, &pool)) return rc;
     Params P{};
     fill_common(P, rows, nrows, links, nlinks, now_ns, out, out_bytes, layout, max_frames, max_ready, flags, res);
     Carver c{static_cast<uint8_t*>(pool->scratch)};
@@ -703,7 +576,7 @@ int dk_tcp_connect_timers(dk_tcp_connector* rows, uint32_t nrows, const dk_tx_li
         hipLaunchKernelGGL(con_expire_kernel, grid_for(nrows), dim3(kBlock), 0, s, P);
     }
     hipLaunchKernelGGL(con_finish_kernel, grid_for(nrows), dim3(kBlock), 0, s, P, nrows);
-    return leave(pool, s);
+    return pool->record(s);
 }
 
 }  // extern "C"

@@ -26,35 +26,29 @@
 //                            only ordering needed.
 // No loop depends on another workgroup's progress: every probe loop is bounded by the table's size and a failed
 // compare-and-swap moves on. Atomics are agent-scope integer __hip_atomic_* on global memory; everything else is
-// plain vector stores.
-// The reply builder is this file's own (62 and 54 bytes, no payload to sum): the existing kernels are untouched.
+// plain vector stores. The replies (62 and 54 bytes, no payload to sum) are ctl_common.h's tcp_frame.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <cerrno>
 #include <cstdint>
 #include <cstring>
 #include <vector>
 
 #include "../../include/dk_tcp.h"
-#include "rx_common.h"
+#include "ctl_common.h"
 
 struct dk_tcp_listen_table {
     int device = 0;
     uint32_t cap = 0;
     dk_tcp_lsn_slot* slots = nullptr;
     uint64_t* consumed = nullptr;  // one device word: never-used slots consumed
-    void* scratch = nullptr;
-    size_t scratch_cap = 0;
-    hipEvent_t last = nullptr;  // serialisation, as a context's
-    hipStream_t last_stream = nullptr;
-    bool used = false;
+    dk::ctl::CallScratch call;  // serialisation, as a context's; its event is made with the table
 };
 
 namespace dk_tcp_listen {
 namespace {
+using namespace dk::ctl;
 
-constexpr uint32_t kBlock = 256, kWave = 64;
 constexpr uint32_t kNone = DK_TCP_LSN_NONE;
 constexpr uint64_t kMatrixBudget = 1u << 22;  // tiles x listeners words of the rank matrix
 constexpr uint32_t kTileMin = 1024;           // frames per tile, at least
@@ -77,15 +71,6 @@ __host__ __device__ inline uint64_t make_key(uint32_t l, uint32_t ip, uint32_t p
 __device__ __forceinline__ uint64_t cas64(uint64_t* p, uint64_t expect, uint64_t want) {
     __hip_atomic_compare_exchange_strong(p, &expect, want, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     return expect;  // the value found
-}
-__device__ __forceinline__ void min32(uint32_t* p, uint32_t v) {
-    __hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ uint32_t add32(uint32_t* p, uint32_t v) {
-    return __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void add64(uint64_t* p, uint64_t v) {
-    __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 struct Params {
@@ -125,19 +110,6 @@ __device__ __forceinline__ bool fits(const Params& P) {
     return dk::tcp_tx_fits(P.tot[0], P.max_frames, P.stride, P.out_bytes) && P.tot[1] <= P.max_ready;
 }
 
-// CRC-32/CKSUM of the 16 bytes isn_generator.rs feeds it (ips in octet order: their first octet is the low byte).
-__device__ uint32_t isn_crc(uint32_t rip, uint32_t rport, uint32_t lip, uint32_t lport, uint32_t nonce) {
-    const uint32_t w[4] = {__builtin_bswap32(rip), (rport & 0xFFFFu) << 16 | (__builtin_bswap32(lip) >> 16),
-                           (__builtin_bswap32(lip) << 16) | (lport & 0xFFFFu), nonce};
-    uint32_t crc = 0;
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        crc ^= w[k];  // four message bytes, most significant first
-        for (int b = 0; b < 32; b++) crc = (crc << 1) ^ ((crc >> 31) ? 0x04C11DB7u : 0u);
-    }
-    return ~crc;
-}
-
 __device__ __forceinline__ uint32_t room_of(const dk_tcp_listener& L) {
     return L.max_backlog > L.inflight ? L.max_backlog - L.inflight : 0u;
 }
@@ -154,64 +126,6 @@ __device__ uint32_t syn_options(const Params& P, uint32_t i) {
         }
     }
     return mss | ws << 16;
-}
-
-__device__ __forceinline__ uint32_t be16s(uint32_t x) { return (x >> 16) + (x & 0xFFFFu); }
-__device__ __forceinline__ uint32_t bsw16(uint32_t x) { return ((x & 0xFFu) << 8) | ((x >> 8) & 0xFFu); }
-__device__ __forceinline__ uint32_t ipbe(uint32_t a) { return bsw16(a & 0xFFFFu) + bsw16(a >> 16); }
-__device__ __forceinline__ uint32_t csum_fold(uint32_t s) {
-    s = (s >> 16) + (s & 0xFFFFu);
-    s = (s >> 16) + (s & 0xFFFFu);
-    return ~s & 0xFFFFu;
-}
-
-// One reply at a: Ethernet2 + IPv4 + TCP with no payload, the bytes dk_tx_serialize writes for the descriptor.
-// synack: options [MSS(mss), WindowScale(ws)], 62 bytes; else 54.
-__device__ void build_reply(uint8_t* a, const dk_tx_link* lk, uint32_t ipw, uint32_t src, uint32_t dst, uint32_t sport,
-                            uint32_t dport, uint32_t seq, uint32_t ack, uint32_t b13, uint32_t win, bool synack,
-                            uint32_t mss, uint32_t ws, bool offload) {
-    const uint32_t* lw = reinterpret_cast<const uint32_t*>(lk);
-    const uint32_t hl = synack ? 28u : 20u, tot = 20u + hl;
-    const uint32_t ident = ipw & 0xFFFFu, ttl = (ipw >> 16) & 0xFFu, tos = ipw >> 24;
-    const uint32_t ipc = csum_fold((0x4500u | tos) + tot + ident + 0x4000u + ((ttl << 8) | 6u) + ipbe(src) + ipbe(dst));
-    const uint32_t b12 = (hl / 4) << 4;
-    uint32_t c = 0;
-    if (!offload) {
-        uint32_t s = ipbe(src) + ipbe(dst) + 6u + hl + sport + dport + be16s(seq) + be16s(ack) + ((b12 << 8) | b13) + win;
-        if (synack) s += 0x0204u + (mss & 0xFFFFu) + 0x0303u + ((ws & 0xFFu) << 8);
-        c = csum_fold(s);
-    }
-    uint32_t d[16];
-    d[0] = lw[0];
-    d[1] = lw[1];
-    d[2] = lw[2];
-    d[3] = 0x0008u | 0x45u << 16 | tos << 24;
-    d[4] = bsw16(tot) | bsw16(ident) << 16;
-    d[5] = 0x0040u | ttl << 16 | 6u << 24;
-    d[6] = bsw16(ipc) | (src & 0xFFFFu) << 16;
-    d[7] = (src >> 16) | (dst & 0xFFFFu) << 16;
-    d[8] = (dst >> 16) | bsw16(sport) << 16;
-    const uint32_t sq = __builtin_bswap32(seq), ak = __builtin_bswap32(ack);
-    d[9] = bsw16(dport) | sq << 16;
-    d[10] = (sq >> 16) | ak << 16;
-    d[11] = (ak >> 16) | b12 << 16 | b13 << 24;
-    d[12] = bsw16(win) | bsw16(c) << 16;
-    d[13] = synack ? 0x0402u << 16 : 0u;  // urgent pointer 0; kind 2, length 4
-    d[14] = bsw16(mss & 0xFFFFu) | 0x0303u << 16;  // the MSS; kind 3, length 3
-    d[15] = ws & 0xFFu;                            // the shift; EndOfOptionsList
-    const uint32_t nb = synack ? DK_TCP_LSN_SYNACK_BYTES : DK_TCP_LSN_RST_BYTES;
-    if ((reinterpret_cast<uintptr_t>(a) & 3u) == 0) {
-        uint32_t* q = reinterpret_cast<uint32_t*>(a);
-#pragma unroll
-        for (int k = 0; k < 15; k++)
-            if ((uint32_t)(4 * k + 4) <= nb) q[k] = d[k];
-        if (synack) *reinterpret_cast<uint16_t*>(a + 60) = (uint16_t)d[15];
-        else *reinterpret_cast<uint16_t*>(a + 52) = (uint16_t)d[13];
-    } else {
-#pragma unroll
-        for (int k = 0; k < 62; k++)
-            if ((uint32_t)k < nb) a[k] = (uint8_t)(d[k >> 2] >> ((k & 3) * 8));
-    }
 }
 
 // The listener checks of dk_tcp.h, in its order.
@@ -494,8 +408,8 @@ __global__ __launch_bounds__(kBlock) void lsn_build_kernel(Params P) {
             P.res.off_out[f] = foff;
             P.res.len_out[f] = (uint16_t)(sa ? DK_TCP_LSN_SYNACK_BYTES : DK_TCP_LSN_RST_BYTES);
             if (P.res.frame_seg) P.res.frame_seg[f] = i;
-            build_reply(P.out + foff, P.links + lk, L.ip_word, L.local_ip, rip, L.local_port, rport, seq, ack, b13, win,
-                        sa, L.advertised_mss, L.window_scale, (P.flags & DK_TX_OFFLOAD_TCP) != 0);
+            tcp_frame(P.out + foff, P.links + lk, L.ip_word, L.local_ip, rip, L.local_port, rport, seq, ack, b13, win, sa,
+                      L.advertised_mss, L.window_scale, (P.flags & DK_TX_OFFLOAD_TCP) != 0);
         } else if (act == DK_TCP_LSN_ESTABLISHED || act == DK_TCP_LSN_ESTABLISHED_DATA || act == DK_TCP_LSN_BAD_ACK) {
             const uint32_t err = act == DK_TCP_LSN_BAD_ACK ? EBADMSG : 0;
             dk_tcp_lsn_ready* R = P.res.ready + P.flag_y[i];
@@ -574,9 +488,9 @@ __global__ __launch_bounds__(kBlock) void lsn_expire_kernel(Params P) {
         P.res.off_out[f] = foff;
         P.res.len_out[f] = (uint16_t)DK_TCP_LSN_SYNACK_BYTES;
         if (P.res.frame_seg) P.res.frame_seg[f] = s;
-        build_reply(P.out + foff, P.links + L.link, L.ip_word, L.local_ip, rip, L.local_port, rport, S.local_isn,
-                    S.remote_isn + 1u, 0x12u, L.receive_window_size, true, L.advertised_mss, L.window_scale,
-                    (P.flags & DK_TX_OFFLOAD_TCP) != 0);
+        tcp_frame(P.out + foff, P.links + L.link, L.ip_word, L.local_ip, rip, L.local_port, rport, S.local_isn,
+                  S.remote_isn + 1u, 0x12u, L.receive_window_size, true, L.advertised_mss, L.window_scale,
+                  (P.flags & DK_TX_OFFLOAD_TCP) != 0);
     } else {
         S.state = DK_TCP_LSN_FAILED;
         S.err = ETIMEDOUT;
@@ -614,54 +528,6 @@ __global__ __launch_bounds__(kBlock) void lsn_release_kernel(dk_tcp_lsn_slot* sl
     found[j] = hit;
 }
 
-struct DeviceGuard {
-    int prev = -1;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) (void)hipSetDevice(dev);
-    }
-    ~DeviceGuard() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
-size_t round16(size_t b) { return (b + 15) & ~(size_t)15; }
-
-struct Carver {
-    uint8_t* b;
-    template <class T>
-    T* take(size_t count) {
-        T* p = reinterpret_cast<T*>(b);
-        b += round16(count * sizeof(T));
-        return p;
-    }
-};
-
-// The table's scratch grown to `need` bytes; waits for in-flight work on the old one first.
-int ensure_scratch(dk_tcp_listen_table* t, size_t need) {
-    if (t->scratch_cap >= need) return 0;
-    if (t->used && hipEventSynchronize(t->last) != hipSuccess) return EIO;
-    if (t->scratch) (void)hipFree(t->scratch);
-    t->scratch = nullptr, t->scratch_cap = 0;
-    if (hipMalloc(&t->scratch, need) != hipSuccess) return ENOMEM;
-    t->scratch_cap = need;
-    return 0;
-}
-
-int enter(dk_tcp_listen_table* t, hipStream_t s) {
-    if (t->used && t->last_stream != s && hipStreamWaitEvent(s, t->last, 0) != hipSuccess) return EIO;
-    return 0;
-}
-int leave(dk_tcp_listen_table* t, hipStream_t s) {
-    if (hipGetLastError() != hipSuccess) return EIO;
-    if (hipEventRecord(t->last, s) != hipSuccess) return EIO;
-    t->last_stream = s;
-    t->used = true;
-    return 0;
-}
-
-dim3 grid_for(uint32_t items) { return dim3((items + kBlock - 1) / kBlock); }
-
 }  // namespace
 }  // namespace dk_tcp_listen
 
@@ -693,7 +559,7 @@ int dk_tcp_listen_table_create(int32_t device, uint32_t cap, dk_tcp_listen_table
     const uint64_t zero = 0;
     if (hipMalloc(&t->slots, (size_t)cap * sizeof(dk_tcp_lsn_slot)) != hipSuccess ||
         hipMalloc(&t->consumed, sizeof(uint64_t)) != hipSuccess ||
-        hipEventCreateWithFlags(&t->last, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&t->call.last, hipEventDisableTiming) != hipSuccess ||
         hipMemcpy(t->slots, rows.data(), rows.size() * sizeof(dk_tcp_lsn_slot), hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(t->consumed, &zero, sizeof(zero), hipMemcpyHostToDevice) != hipSuccess) {
         dk_tcp_listen_table_destroy(t);
@@ -705,21 +571,21 @@ int dk_tcp_listen_table_create(int32_t device, uint32_t cap, dk_tcp_listen_table
 
 void dk_tcp_listen_table_destroy(dk_tcp_listen_table* t) {
     if (!t) return;
-    dk_tcp_listen::DeviceGuard g(t->device);
-    if (t->used) (void)hipEventSynchronize(t->last);
+    dk::ctl::DeviceGuard g(t->device);
+    if (t->call.used) (void)hipEventSynchronize(t->call.last);
     if (t->slots) (void)hipFree(t->slots);
     if (t->consumed) (void)hipFree(t->consumed);
-    if (t->scratch) (void)hipFree(t->scratch);
-    if (t->last) (void)hipEventDestroy(t->last);
+    if (t->call.scratch) (void)hipFree(t->call.scratch);
+    if (t->call.last) (void)hipEventDestroy(t->call.last);
     delete t;
 }
 
 int dk_tcp_listen_table_stats(dk_tcp_listen_table* t, uint32_t* cap, uint64_t* consumed) {
     if (!t) return EINVAL;
-    dk_tcp_listen::DeviceGuard g(t->device);
+    dk::ctl::DeviceGuard g(t->device);
     if (cap) *cap = t->cap;
     if (consumed) {
-        if (t->used && hipEventSynchronize(t->last) != hipSuccess) return EIO;
+        if (t->call.used && hipEventSynchronize(t->call.last) != hipSuccess) return EIO;
         if (hipMemcpy(consumed, t->consumed, sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess) return EIO;
     }
     return 0;
@@ -727,16 +593,16 @@ int dk_tcp_listen_table_stats(dk_tcp_listen_table* t, uint32_t* cap, uint64_t* c
 
 int dk_tcp_listen_table_read(dk_tcp_listen_table* t, dk_tcp_lsn_slot* rows) {
     if (!t || !rows) return EINVAL;
-    dk_tcp_listen::DeviceGuard g(t->device);
-    if (t->used && hipEventSynchronize(t->last) != hipSuccess) return EIO;
+    dk::ctl::DeviceGuard g(t->device);
+    if (t->call.used && hipEventSynchronize(t->call.last) != hipSuccess) return EIO;
     return hipMemcpy(rows, t->slots, (size_t)t->cap * sizeof(dk_tcp_lsn_slot), hipMemcpyDeviceToHost) == hipSuccess ? 0
                                                                                                                      : EIO;
 }
 
 int dk_tcp_listen_table_write(dk_tcp_listen_table* t, const dk_tcp_lsn_slot* rows) {
     if (!t || !rows) return EINVAL;
-    dk_tcp_listen::DeviceGuard g(t->device);
-    if (t->used && hipEventSynchronize(t->last) != hipSuccess) return EIO;
+    dk::ctl::DeviceGuard g(t->device);
+    if (t->call.used && hipEventSynchronize(t->call.last) != hipSuccess) return EIO;
     uint64_t consumed = 0;
     for (uint32_t s = 0; s < t->cap; s++) consumed += rows[s].state != DK_TCP_LSN_FREE;
     if (hipMemcpy(t->slots, rows, (size_t)t->cap * sizeof(dk_tcp_lsn_slot), hipMemcpyHostToDevice) != hipSuccess ||
@@ -774,8 +640,8 @@ int dk_tcp_listen_process(dk_tcp_listen_table* t, const dk_rx_results* rx, uint3
     const size_t zero_bytes = round16((size_t)ntiles * nl * 4) + 2 * round16((size_t)nl * 4) + round16(8) + round16(16);
     const size_t need = ff_bytes + zero_bytes + 5 * round16((size_t)n * 4) + round16(n) + 2 * round16((size_t)n * 8) +
                         round16((size_t)sb * 8) + 16;
-    if (int rc = ensure_scratch(t, need)) return rc;
-    if (enter(t, s)) return EIO;
+    if (int rc = t->call.grow(need)) return rc;
+    if (t->call.order(s)) return EIO;
     Params P{};
     P.slots = t->slots, P.consumed = t->consumed, P.cap = t->cap;
     P.rx = *rx, P.n = n, P.lst = listeners, P.nl = nl, P.lsn_of_flow = lsn_of_flow, P.nflows = nflows;
@@ -783,7 +649,7 @@ int dk_tcp_listen_process(dk_tcp_listen_table* t, const dk_rx_results* rx, uint3
     P.out = out, P.out_bytes = out_bytes, P.stride = layout->slot_stride, P.lead = layout->frame_lead;
     P.max_frames = max_frames, P.max_ready = max_ready, P.flags = flags, P.res = *res;
     P.H = H, P.tile = tile, P.ntiles = ntiles;
-    Carver c{static_cast<uint8_t*>(t->scratch)};
+    Carver c{static_cast<uint8_t*>(t->call.scratch)};
     uint8_t* ff = c.b;
     P.gkey = c.take<uint64_t>(H);
     P.gfirst = c.take<uint32_t>(H);
@@ -823,8 +689,8 @@ int dk_tcp_listen_process(dk_tcp_listen_table* t, const dk_rx_results* rx, uint3
             hipMemsetAsync(res->reply_frame, 0xFF, (size_t)n * 4, s) != hipSuccess)
             return EIO;
     }
-    hipLaunchKernelGGL(lsn_finish_kernel, grid_for(std::max(nl, 1u)), dim3(kBlock), 0, s, P);
-    return leave(t, s);
+    hipLaunchKernelGGL(lsn_finish_kernel, grid_for(nl), dim3(kBlock), 0, s, P);
+    return t->call.record(s);
 }
 
 int dk_tcp_listen_timers(dk_tcp_listen_table* t, const dk_tcp_listener* listeners, uint32_t nl, uint64_t backlog_sum,
@@ -843,15 +709,15 @@ int dk_tcp_listen_timers(dk_tcp_listen_table* t, const dk_tcp_listener* listener
     const uint32_t cap = t->cap, sb = dk_tcp_tx_scan_tiles(cap);
     const size_t zero_bytes = round16((size_t)nl * 4) + round16(16);
     const size_t need = zero_bytes + 2 * round16((size_t)cap * 8) + round16((size_t)sb * 8) + 16;
-    if (int rc = ensure_scratch(t, need)) return rc;
-    if (enter(t, s)) return EIO;
+    if (int rc = t->call.grow(need)) return rc;
+    if (t->call.order(s)) return EIO;
     Params P{};
     P.slots = t->slots, P.consumed = t->consumed, P.cap = cap;
     P.lst = const_cast<dk_tcp_listener*>(listeners), P.nl = nl;  // lcand == nullptr: the finish kernel writes no row
     P.links = links, P.nlinks = nlinks, P.now = now_ns;
     P.out = out, P.out_bytes = out_bytes, P.stride = layout->slot_stride, P.lead = layout->frame_lead;
     P.max_frames = max_frames, P.max_ready = max_ready, P.flags = flags, P.res = *res;
-    Carver c{static_cast<uint8_t*>(t->scratch)};
+    Carver c{static_cast<uint8_t*>(t->call.scratch)};
     uint8_t* zz = c.b;
     P.lwork = c.take<uint32_t>(nl);
     P.tot = c.take<uint64_t>(2);
@@ -866,8 +732,8 @@ int dk_tcp_listen_timers(dk_tcp_listen_table* t, const dk_tcp_listener* listener
         if (dk_tcp_tx_scan(P.flag_r, cap, bsum, P.tot, s) || dk_tcp_tx_scan(P.flag_y, cap, bsum, P.tot + 1, s)) return EIO;
         hipLaunchKernelGGL(lsn_expire_kernel, grid_for(cap), dim3(kBlock), 0, s, P);
     }
-    hipLaunchKernelGGL(lsn_finish_kernel, grid_for(std::max(nl, 1u)), dim3(kBlock), 0, s, P);
-    return leave(t, s);
+    hipLaunchKernelGGL(lsn_finish_kernel, grid_for(nl), dim3(kBlock), 0, s, P);
+    return t->call.record(s);
 }
 
 int dk_tcp_listen_release(dk_tcp_listen_table* t, dk_tcp_listener* listeners, uint32_t nl, const uint64_t* keys,
@@ -878,10 +744,10 @@ int dk_tcp_listen_release(dk_tcp_listen_table* t, dk_tcp_listener* listeners, ui
     if (reinterpret_cast<uintptr_t>(listeners) & 15) return EINVAL;
     DeviceGuard g(t->device);
     const hipStream_t s = (hipStream_t)stream;
-    if (enter(t, s)) return EIO;
+    if (t->call.order(s)) return EIO;
     if (nkeys) hipLaunchKernelGGL(lsn_release_kernel, grid_for(nkeys), dim3(kBlock), 0, s, t->slots, t->cap, listeners, nl,
                                   keys, nkeys, found);
-    return leave(t, s);
+    return t->call.record(s);
 }
 
 }  // extern "C"

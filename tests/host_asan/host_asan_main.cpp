@@ -1,6 +1,7 @@
 // TEST INFRASTRUCTURE ONLY: driver for the ASan + UBSan build of the product's host-side code (tests/host_asan/Makefile):
-// ring_host.cpp (TPACKET_V3 block walker), demi_host.cpp (results -> demi_sgarray_t) and the host chunk planner of
-// dk_rx_process_host (rx_plan.h), compiled with -fsanitize=address,undefined. tests/test_host_asan.py feeds it valid,
+// ring_host.cpp (TPACKET_V3 block walker), demi_host.cpp (results -> demi_sgarray_t), the host chunk planner of
+// dk_rx_process_host (rx_plan.h) and the control-plane kernels' frame builder and ISN CRC (ctl_common.h), compiled with
+// -fsanitize=address,undefined. tests/test_host_asan.py feeds it valid,
 // corrupted and fuzzed inputs and compares its outputs with the regular build of libdk_rx.so.
 //
 //   host_asan ring    in out   in:  u64 ring_bytes | u32 block_size | u32 first | u32 nblocks | u32 cap | ring bytes
@@ -20,6 +21,12 @@
 //   host_asan ltable  in out   in:  u32 cap | u32 cfg_ip | slots u32[4 cap] (the Active table's open-addressing slots)
 //                              out: i32 built | u32 n | u32 nbuckets | u32 nwords | words u32[nwords]
 //                              (the LDS Active table builder of lds_table.h)
+//   host_asan frame   in out   in:  u32 ncases | per case u32[20]: dst offset (0..3 from a 4-byte boundary), dk_tx_link
+//                                   (4 words), ip_word, src, dst, sport, dport, seq, ack, flags byte, window, options
+//                                   present, mss, ws, offload, ISN nonce, ISN counter
+//                              out: per case: u32 isn (isn_crc(dst, dport, src, sport, nonce) + counter) | u32 nbytes |
+//                                   16 canary bytes (0xA5), the offset's canary bytes, the frame, 16 canary bytes
+//                              (tcp_frame and isn_crc of ctl_common.h; the buffer ends with the back canary)
 #include <cerrno>
 #include <cstdint>
 #include <cstdio>
@@ -27,6 +34,7 @@
 #include <cstring>
 #include <vector>
 
+#include "../../demikernel_amd/csrc/ctl_common.h"
 #include "../../demikernel_amd/csrc/lds_table.h"
 #include "../../demikernel_amd/csrc/rx_plan.h"
 #include "../../include/dk_demi.h"
@@ -201,11 +209,29 @@ int do_utable() {
     if (ok) wr(words.data(), words.size());
     return 0;
 }
+int do_frame() {
+    constexpr uint32_t kPad = 16;
+    const uint32_t ncases = rd1<uint32_t>();
+    for (uint32_t i = 0; i < ncases; i++) {
+        uint32_t w[20];
+        rd(w, 20);
+        dk_tx_link lk;
+        memcpy(&lk, w + 1, sizeof lk);
+        const uint32_t at = kPad + (w[0] & 3u), nb = w[14] ? dk::ctl::kTcpOptFrameBytes : dk::ctl::kTcpFrameBytes;
+        std::vector<uint8_t> buf(at + nb + kPad, 0xA5);  // the heap block starts on a 16-byte boundary
+        dk::ctl::tcp_frame(buf.data() + at, &lk, w[5], w[6], w[7], w[8], w[9], w[10], w[11], w[12], w[13], w[14] != 0, w[15],
+                           w[16], w[17] != 0);
+        wr1<uint32_t>(dk::ctl::isn_crc(w[7], w[9], w[6], w[8], w[18]) + (uint32_t)(uint16_t)w[19]);
+        wr1<uint32_t>((uint32_t)buf.size());
+        wr(buf.data(), buf.size());
+    }
+    return 0;
+}
 }  // namespace
 
 int main(int argc, char** argv) {
     if (argc != 4) {
-        fprintf(stderr, "usage: %s ring|release|udp|tcp|plan|ltable|utable in out\n", argv[0]);
+        fprintf(stderr, "usage: %s ring|release|udp|tcp|plan|ltable|utable|frame in out\n", argv[0]);
         return 2;
     }
     g_in = fopen(argv[2], "rb");
@@ -213,7 +239,8 @@ int main(int argc, char** argv) {
     if (!g_in || !g_out) return 2;
     const char* m = argv[1];
     int rc = !strcmp(m, "ring") ? do_ring(false) : !strcmp(m, "release") ? do_ring(true) : !strcmp(m, "udp") ? do_udp()
-             : !strcmp(m, "tcp") ? do_tcp() : !strcmp(m, "plan") ? do_plan() : !strcmp(m, "ltable") ? do_ltable() : !strcmp(m, "utable") ? do_utable() : 2;
+             : !strcmp(m, "tcp") ? do_tcp() : !strcmp(m, "plan") ? do_plan() : !strcmp(m, "ltable") ? do_ltable() : !strcmp(m, "utable") ? do_utable()
+             : !strcmp(m, "frame") ? do_frame() : 2;
     fclose(g_out);
     fclose(g_in);
     return rc;

@@ -1,6 +1,7 @@
 """The product's host-side code under AddressSanitizer + UndefinedBehaviorSanitizer (CPU only): ring_host.cpp (the
-TPACKET_V3 block walker over caller memory), demi_host.cpp (results -> demi_sgarray_t) and dk_rx_process_host's chunk
-planner (rx_plan.h), built into a standalone driver (tests/host_asan). Valid, corrupted and fuzzed inputs; every
+TPACKET_V3 block walker over caller memory), demi_host.cpp (results -> demi_sgarray_t), dk_rx_process_host's chunk
+planner (rx_plan.h) and the control-plane kernels' frame builder and ISN CRC (ctl_common.h), built into a standalone
+driver (tests/host_asan). Valid, corrupted and fuzzed inputs; every
 sanitizer report aborts the driver (-fno-sanitize-recover), and its outputs must equal the regular libdk_rx.so's on
 the same inputs (the reference's host side is catpowder/linux/mod.rs:138-159 and runtime/memory/mod.rs:38-54)."""
 import ctypes
@@ -12,6 +13,8 @@ import numpy as np
 import pytest
 
 import demux_keys as DK
+import tcp_listen_reference as TLR
+import tx_reference as TR
 from demikernel_amd import _native as N
 from demikernel_amd import ring as RG
 from demikernel_amd import synth
@@ -412,3 +415,84 @@ def test_crafted_tables_host_builders_agree(driver, tmp_path, name):
         assert ok and (mask, seed) == (15, 3)
     if name in ("udp_fid_edge_fffe", "udp_fid_edge_ffff"):
         assert ok == (name == "udp_fid_edge_fffe")
+
+
+# --- the control-plane kernels' frame builder and ISN CRC (ctl_common.h) ------------------------------------------
+F32, F16 = 0xFFFFFFFF, 0xFFFF
+FRAME_BASE = dict(off=0, dst_mac=bytes([2, 0, 0, 0, 0, 9]), src_mac=bytes([2, 0x1B, 0x2C, 0x3D, 0x4E, 0x5F]),
+                  ipw=0x00FF0000 | 0x1234, src=0x0201A8C0, dst=0x0A01A8C0, sport=80, dport=40001, seq=0x01020304,
+                  ack=0xA0B0C0D0, b13=0x10, win=0x2000, opts=0, mss=1460, ws=7, offload=0, nonce=0xDEADBEEF, counter=3)
+
+
+def _frame_cases():
+    """Every variant below under options on / off x offload on / off x the four alignments, then seeded random ones."""
+    variants = [dict(seq=a, ack=b) for a in (0, 0x7FFFFFFF, 0x80000000, F32) for b in (0, 0x7FFFFFFF, 0x80000000, F32)]
+    variants += [dict(sport=a, dport=b, win=c) for a in (0, F16) for b in (0, F16) for c in (0, F16)]
+    variants += [dict(src=a, dst=b) for a in (0, F32) for b in (0, F32)]
+    variants += [dict(mss=a, ws=b) for a in (0, 536, F16) for b in (0, 14)]
+    variants += [dict(ipw=i | t << 16 | o << 24) for i in (0, F16) for t in (0, 0xFF) for o in (0, 0xFF)]
+    # SYN, SYN+ACK, ACK, and listen's two RST+ACK forms (seq = the segment's ACK; seq 0 for a segment without one)
+    variants += [dict(b13=0x02, ack=0), dict(b13=0x12), dict(b13=0x10), dict(b13=0x14, seq=77, ack=78),
+                 dict(b13=0x14, seq=0, ack=0x90000014)]
+    variants += [dict(src=F32, dst=F32, sport=F16, dport=F16, seq=F32, ack=F32, b13=0xFF, win=F16, mss=F16, ws=0xFF,
+                      ipw=F32, dst_mac=b"\xff" * 6, src_mac=b"\xff" * 6, nonce=F32, counter=F16),
+                 dict(src=0, dst=0, sport=0, dport=0, seq=0, ack=0, b13=0, win=0, mss=0, ws=0, ipw=0, dst_mac=bytes(6),
+                      src_mac=bytes(6), nonce=0, counter=0)]
+    cases = [dict(FRAME_BASE, **v, opts=o, offload=f, off=a) for v in variants for o in (0, 1) for f in (0, 1)
+             for a in (0, 1, 2, 3)]
+    rng = np.random.default_rng(21)
+    for _ in range(300):
+        r32 = lambda: int(rng.integers(0, 2**32))  # noqa: E731
+        r16 = lambda: int(rng.integers(0, 2**16))  # noqa: E731
+        cases.append(dict(off=int(rng.integers(0, 4)), dst_mac=rng.bytes(6), src_mac=rng.bytes(6), ipw=r32(), src=r32(),
+                          dst=r32(), sport=r16(), dport=r16(), seq=r32(), ack=r32(), b13=int(rng.integers(0, 256)),
+                          win=r16(), opts=int(rng.integers(0, 2)), mss=r16(), ws=int(rng.integers(0, 15)),
+                          offload=int(rng.integers(0, 2)), nonce=r32(), counter=r16()))
+    return cases
+
+
+@pytest.fixture(scope="module")
+def frame_run(driver, tmp_path_factory):
+    """One driver run over every case: [(case, isn, the bytes before the frame, the frame, the bytes behind it)]."""
+    cases = _frame_cases()
+    blob = np.array([len(cases)], np.uint32).tobytes()
+    for c in cases:
+        blob += (np.array([c["off"]], np.uint32).tobytes() + c["dst_mac"] + c["src_mac"] + bytes(4) +
+                 np.array([c[k] for k in ("ipw", "src", "dst", "sport", "dport", "seq", "ack", "b13", "win", "opts", "mss",
+                                          "ws", "offload", "nonce", "counter")], np.uint32).tobytes())
+    out = run(driver, "frame", blob, tmp_path_factory.mktemp("frame"))
+    rows, p = [], 0
+    for c in cases:
+        isn, nbytes = (int(x) for x in np.frombuffer(out[p:p + 8], np.uint32))
+        buf = out[p + 8:p + 8 + nbytes]
+        nb = 62 if c["opts"] else 54
+        assert nbytes == 16 + c["off"] + nb + 16, (c, nbytes)
+        rows.append((c, isn, buf[:16 + c["off"]], buf[16 + c["off"]:16 + c["off"] + nb], buf[16 + c["off"] + nb:]))
+        p += 8 + nbytes
+    assert p == len(out)
+    return rows
+
+
+def test_frame_builder_bytes(frame_run):
+    """tcp_frame against tx_reference.headers for the same descriptor: 54 bytes, or 62 with [MSS, WindowScale]; a zero
+    TCP checksum under the offload flag; nothing stored in front of the frame or past its last byte, at any of the four
+    alignments (offset 0 takes the dword stores, 1 to 3 the byte stores)."""
+    assert len(frame_run) >= 300 + 16 * 40 and {c["off"] for c, *_ in frame_run} == {0, 1, 2, 3}
+    for c, _, front, frame, back in frame_run:
+        options = bytes([2, 4]) + c["mss"].to_bytes(2, "big") + bytes([3, 3, c["ws"], 0]) if c["opts"] else b""
+        exp = TR.headers(b"", 6, c["src"], c["dst"], c["sport"] | c["dport"] << 16, meta=c["b13"] << 16, seq=c["seq"],
+                         ack=c["ack"], winurg=c["win"], options=options, ipw=c["ipw"], dst_mac=c["dst_mac"],
+                         src_mac=c["src_mac"], flags=TR.OFFLOAD_TCP if c["offload"] else 0)
+        assert len(exp) == (62 if c["opts"] else 54)
+        assert frame == exp, (c, frame.hex(), exp.hex())
+        if c["offload"]:
+            assert frame[50:52] == b"\0\0"
+        assert front == b"\xa5" * len(front) and back == b"\xa5" * 16, c
+
+
+def test_isn_crc(frame_run):
+    """isn_crc + the counter against CRC-32/CKSUM of the 16 bytes the ISN generator hashes (remote = the frame's
+    destination, local = its source)."""
+    for c, isn, *_ in frame_run:
+        L = dict(local_ip=c["src"], local_port=c["sport"], nonce=c["nonce"])
+        assert isn == (TLR.crc32_cksum(TLR.isn_bytes(L, c["dst"], c["dport"])) + c["counter"]) & F32, c
