@@ -205,17 +205,21 @@ def arp_timers(table: ArpTable, rows, links, now_ns: int, out, res: ArpResults, 
 
 def arp_lookup(table: ArpTable, ips, links=None, link=None, stream=None, fill: int = 0):
     """dk_arp_lookup of `ips` (an iterable of addresses); link: per-address link indices (NO_LINK: none). Returns
-    (found u32[n], macs u8[n, 6]) as whole canary-filled arrays cut to n (waits for the call)."""
+    (found u32[n], macs u8[n, 6]) as whole canary-filled arrays cut to n (waits for the call). The addresses and link
+    indices are uploaded and the two arrays made, filled and read back on `stream` (default: the current stream), the
+    stream the call runs on; `links` must be ready on it. For the asynchronous calls above the same holds for
+    everything the caller passes in, their result objects included: tensors made or filled on another stream need that
+    stream waited for before the call."""
     import torch
 
     a = np.asarray(list(ips), np.uint32)
     dev = torch.device("cuda", table.device)
-    ad = torch.from_numpy(a.view(np.int32).copy()).to(dev)
-    ld = None if link is None else torch.from_numpy(np.asarray(list(link), np.uint32).view(np.int32).copy()).to(dev)
-    found = torch.full((4 * max(len(a), 1),), fill, dtype=torch.uint8, device=dev)
-    macs = torch.full((6 * max(len(a), 1),), fill, dtype=torch.uint8, device=dev)
     s = _stream(stream, table.device)
-    _check(table.lib.dk_arp_lookup(table._t, _ptr(ad), _ptr(ld), len(a), _ptr(links), _nlinks(links), _ptr(macs),
-                                   _ptr(found), ctypes.c_void_p(s.cuda_stream)), "dk_arp_lookup")
-    s.synchronize()
-    return found.cpu().numpy().view(np.uint32)[:len(a)], macs.cpu().numpy().reshape(-1, 6)[:len(a)]
+    with torch.cuda.stream(s):
+        ad = torch.from_numpy(a.view(np.int32).copy()).to(dev)
+        ld = None if link is None else torch.from_numpy(np.asarray(list(link), np.uint32).view(np.int32).copy()).to(dev)
+        found = torch.full((4 * max(len(a), 1),), fill, dtype=torch.uint8, device=dev)
+        macs = torch.full((6 * max(len(a), 1),), fill, dtype=torch.uint8, device=dev)
+        _check(table.lib.dk_arp_lookup(table._t, _ptr(ad), _ptr(ld), len(a), _ptr(links), _nlinks(links), _ptr(macs),
+                                       _ptr(found), ctypes.c_void_p(s.cuda_stream)), "dk_arp_lookup")
+        return found.cpu().numpy().view(np.uint32)[:len(a)], macs.cpu().numpy().reshape(-1, 6)[:len(a)]

@@ -100,14 +100,18 @@ def close_start(rows, rx_conns, tx_conns, close, *, nclose: Optional[int] = None
                 stream=None) -> CloseStart:
     """dk_tcp_close_start: rows / rx_conns / tx_conns uint8 device tensors of CLOSER_DTYPE / CONN_DTYPE / TX_CONN_DTYPE
     rows (the first two updated in place), close the int32 / uint32 device array of connections, strictly ascending.
-    Returns the statuses and the marker list; nothing is read back."""
+    Returns the statuses and the marker list; nothing is read back. The returned tensors are made and filled on
+    `stream` (default: the current stream), the stream the call runs on: a reader on another stream waits for `stream`
+    first. What the caller passes in (here and in close_process / close_timers, their result objects included) must be
+    ready on `stream`: tensors made or filled on another stream need that stream waited for before the call."""
     import torch
 
     s = _stream(stream, device)
     k = close.numel() if nclose is None else nclose
     i32 = lambda m: torch.full((4 * max(m, 1),), fill, dtype=torch.uint8,  # noqa: E731
                                device=torch.device("cuda", device)).view(torch.int32)
-    status, conn, off, lens, nm = i32(k), i32(k), i32(k), i32(k), i32(1)
+    with torch.cuda.stream(s):  # the fills are ordered before the call's stores, and the allocator knows the stream
+        status, conn, off, lens, nm = i32(k), i32(k), i32(k), i32(k), i32(1)
     _check(N.load_library().dk_tcp_close_start(
         _ptr(rows), _ptr(rx_conns), _ptr(tx_conns), _nconns(rows), _ptr(close), k, _ptr(status), _ptr(conn), _ptr(off),
         _ptr(lens), _ptr(nm), ctypes.c_void_p(s.cuda_stream)), "dk_tcp_close_start")

@@ -107,7 +107,10 @@ def connect_start(rows, start, gen, links, now_ns: int, out, res: ConnectResults
                   frame_lead: int = 0, flags: int = 0, nstart: Optional[int] = None, out_bytes=None, max_frames=None,
                   max_ready=None, device: int = 0, stream=None) -> None:
     """dk_tcp_connect_start: rows a uint8 device tensor of CONNECTOR_DTYPE rows (updated in place), start the int32 /
-    uint32 device array of row indices in connect-call order, gen the device ISN_GEN_DTYPE row (updated in place)."""
+    uint32 device array of row indices in connect-call order, gen the device ISN_GEN_DTYPE row (updated in place).
+    Asynchronous on `stream` (default: the current stream), as connect_process and connect_timers are; the wrappers make
+    no tensor of their own. Everything the caller passes in, `res` included, must be ready on `stream`: tensors made or
+    filled on another stream need that stream waited for before the call."""
     s = _stream(stream, device)
     o = res.c_struct()
     lay = N.DkTcpTxLayout(slot_stride, frame_lead)

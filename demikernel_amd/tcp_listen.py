@@ -161,12 +161,17 @@ def listen_process(table: ListenTable, rx: RxResults, listeners, lsn_map, links,
                    stream=None) -> None:
     """dk_tcp_listen_process: `rx` are the results of the batch's receive_batch call (tcp_fields and tcp_opts on),
     listeners a uint8 device tensor of LISTENER_DTYPE rows (updated in place), lsn_map the int32 / uint32 device map
-    flow_id -> listener row. backlog_sum defaults to the rows' sum (read back from the device: pass it to stay
-    asynchronous)."""
+    flow_id -> listener row. backlog_sum defaults to the rows' sum (read back from the device, on `stream`: pass it to
+    stay asynchronous). Everything the caller passes in, `res` included, must be ready on `stream` (default: the current
+    stream): tensors made or filled on another stream need that stream waited for before the call. The same holds for
+    listen_timers."""
+    import torch
+
     nl = listeners.numel() // LISTENER_DTYPE.itemsize
-    if backlog_sum is None:
-        backlog_sum = int(listeners_to_host(listeners)["max_backlog"].astype(np.uint64).sum())
     s = _stream(stream, table.device)
+    if backlog_sum is None:
+        with torch.cuda.stream(s):  # behind the calls that update the rows, which run on this stream
+            backlog_sum = int(listeners_to_host(listeners)["max_backlog"].astype(np.uint64).sum())
     r, o = rx.c_struct(), res.c_struct()
     lay = N.DkTcpTxLayout(slot_stride, frame_lead)
     _check(table.lib.dk_tcp_listen_process(
@@ -193,19 +198,21 @@ def listen_timers(table: ListenTable, listeners, links, now_ns: int, out, res: L
 
 
 def listen_release(table: ListenTable, listeners, keys, stream=None) -> np.ndarray:
-    """dk_tcp_listen_release of `keys` (an iterable of key words); returns found[] (waits for the call)."""
+    """dk_tcp_listen_release of `keys` (an iterable of key words); returns found[] (waits for the call). The keys are
+    uploaded and found[] is made, filled and read back on `stream` (default: the current stream), the stream the call
+    runs on; `listeners` must be ready on it."""
     import torch
 
     k = np.asarray(list(keys), np.uint64)
     dev = torch.device("cuda", table.device)
-    kd = torch.from_numpy(k.view(np.int64).copy()).to(dev)
-    found = torch.full((max(len(k), 1),), 0x5A5A5A5A, dtype=torch.int32, device=dev)
     nl = listeners.numel() // LISTENER_DTYPE.itemsize
     s = _stream(stream, table.device)
-    _check(table.lib.dk_tcp_listen_release(table._t, _ptr(listeners), nl, _ptr(kd), len(k), _ptr(found),
-                                           ctypes.c_void_p(s.cuda_stream)), "dk_tcp_listen_release")
-    s.synchronize()
-    return found.cpu().numpy().view(np.uint32)[:len(k)]
+    with torch.cuda.stream(s):
+        kd = torch.from_numpy(k.view(np.int64).copy()).to(dev)
+        found = torch.full((max(len(k), 1),), 0x5A5A5A5A, dtype=torch.int32, device=dev)
+        _check(table.lib.dk_tcp_listen_release(table._t, _ptr(listeners), nl, _ptr(kd), len(k), _ptr(found),
+                                               ctypes.c_void_p(s.cuda_stream)), "dk_tcp_listen_release")
+        return found.cpu().numpy().view(np.uint32)[:len(k)]
 
 
 def conn_rows_from_ready(rec, listener_row, *, buffer_size: Optional[int] = None, link: Optional[int] = None):

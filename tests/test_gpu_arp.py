@@ -14,6 +14,7 @@ import frames as F
 from demikernel_amd import Config, FrameBatch, RxEngine, ipv4, synth
 from demikernel_amd import _native as N
 from demikernel_amd import arp as ARP
+from ctl_calls import run
 
 pytestmark = pytest.mark.gpu
 
@@ -58,7 +59,7 @@ class Device:
         if self.d_links is not None:
             assert self.d_links.cpu().numpy().tobytes() == self.model.links.tobytes(), "links[] differ"
 
-    def _compare(self, got, exp, slot_stride, frame_lead, per_frame):
+    def _compare(self, got, exp, slot_stride, frame_lead, per_frame, state=True):
         assert (got["n_frames"], got["n_ready"], got["n_entries"]) == (exp["n_frames"], exp["n_ready"], exp["n_entries"])
         assert np.array_equal(got["status"], exp["status"]), (got["status"], exp["status"])
         if per_frame and exp["fits"]:
@@ -81,9 +82,17 @@ class Device:
             bad = np.nonzero(got["out"] != want)[0]
             raise AssertionError(f"{len(bad)} output bytes differ, first at {bad[:8]}: got {got['out'][bad[:8]]} "
                                  f"expected {want[bad[:8]]}")
-        self.compare_state()
+        if state:
+            self.compare_state()
 
-    def process(self, frames, clock, *, slot_stride=64, frame_lead=0, max_frames=None, max_ready=None, out_bytes=None):
+    def process(self, frames, clock, **kw):
+        return run(self.process_steps(frames, clock, **kw))
+
+    def process_steps(self, frames, clock, *, slot_stride=64, frame_lead=0, max_frames=None, max_ready=None,
+                      out_bytes=None, stream=None, state=True):
+        """process() in the three steps of ctl_calls.Call: the uploads and fills, the call (on `stream`), the wait and
+        the comparison. state=False leaves the table, rows and links to a later call's comparison. The same for start
+        and timers."""
         import torch
 
         n = len(frames)
@@ -104,8 +113,11 @@ class Device:
         d_out = self._out(max_frames, slot_stride)
         ob = d_out.numel() if out_bytes is None else out_bytes
         res = ARP.ArpResults(n, max_frames, max_ready, 1, fill=FILL)
+        yield
         ARP.arp_process(self.table, batch, rx, self.d_rows, self.d_links, clock, d_out, res, slot_stride=slot_stride,
-                        frame_lead=frame_lead, n=n, out_bytes=ob, max_frames=max_frames, max_ready=max_ready)
+                        frame_lead=frame_lead, n=n, out_bytes=ob, max_frames=max_frames, max_ready=max_ready,
+                        stream=stream)
+        yield
         torch.cuda.synchronize()
         exp = self.model.process(mf, clock, slot_stride=slot_stride, frame_lead=frame_lead, max_frames=max_frames,
                                  out_bytes=ob, max_ready=max_ready)
@@ -115,10 +127,14 @@ class Device:
         for k in RX_KEYS:
             assert before[k].tobytes() == after[k].tobytes(), f"the batch's {k} was written"
         assert np.array_equal(batch.blob.cpu().numpy(), blob) and np.array_equal(batch.off.cpu().numpy().view(np.uint32), off)
-        self._compare(got, exp, slot_stride, frame_lead, per_frame=True)
+        self._compare(got, exp, slot_stride, frame_lead, per_frame=True, state=state)
         return got, exp
 
-    def start(self, start, now, *, slot_stride=64, frame_lead=0, max_frames=None, max_ready=None, out_bytes=None):
+    def start(self, start, now, **kw):
+        return run(self.start_steps(start, now, **kw))
+
+    def start_steps(self, start, now, *, slot_stride=64, frame_lead=0, max_frames=None, max_ready=None, out_bytes=None,
+                    stream=None, state=True):
         import torch
 
         ns = len(start)
@@ -128,8 +144,11 @@ class Device:
         ob = d_out.numel() if out_bytes is None else out_bytes
         res = ARP.ArpResults(4, max_frames, max_ready, max(ns, 1), fill=FILL)
         d_start = ARP.to_device(np.asarray(start, np.uint32)) if ns else torch.zeros(4, dtype=torch.uint8, device="cuda:0")
+        yield
         ARP.arp_query_start(self.table, self.d_rows, d_start, self.d_links, now, d_out, res, slot_stride=slot_stride,
-                            frame_lead=frame_lead, nstart=ns, out_bytes=ob, max_frames=max_frames, max_ready=max_ready)
+                            frame_lead=frame_lead, nstart=ns, out_bytes=ob, max_frames=max_frames, max_ready=max_ready,
+                            stream=stream)
+        yield
         torch.cuda.synchronize()
         exp = self.model.start(start, now, slot_stride=slot_stride, frame_lead=frame_lead, max_frames=max_frames,
                                out_bytes=ob, max_ready=max_ready)
@@ -138,30 +157,37 @@ class Device:
         if ns == 0:
             assert (got["status"] == FILL32).all()
             got["status"] = got["status"][:0]
-        self._compare(got, exp, slot_stride, frame_lead, per_frame=False)
+        self._compare(got, exp, slot_stride, frame_lead, per_frame=False, state=state)
         return got, exp
 
-    def timers(self, now, *, slot_stride=64, frame_lead=0, max_frames=64, max_ready=64, out_bytes=None):
+    def timers(self, now, **kw):
+        return run(self.timers_steps(now, **kw))
+
+    def timers_steps(self, now, *, slot_stride=64, frame_lead=0, max_frames=64, max_ready=64, out_bytes=None, stream=None,
+                     state=True):
         import torch
 
         d_out = self._out(max_frames, slot_stride)
         ob = d_out.numel() if out_bytes is None else out_bytes
         res = ARP.ArpResults(4, max_frames, max_ready, 1, fill=FILL)
+        yield
         ARP.arp_timers(self.table, self.d_rows, self.d_links, now, d_out, res, slot_stride=slot_stride,
-                       frame_lead=frame_lead, out_bytes=ob, max_frames=max_frames, max_ready=max_ready)
+                       frame_lead=frame_lead, out_bytes=ob, max_frames=max_frames, max_ready=max_ready, stream=stream)
+        yield
         torch.cuda.synchronize()
         exp = self.model.timers(now, slot_stride=slot_stride, frame_lead=frame_lead, max_frames=max_frames, out_bytes=ob,
                                 max_ready=max_ready)
         got = res.to_numpy()
         got["out"] = d_out.cpu().numpy()
-        self._compare(got, exp, slot_stride, frame_lead, per_frame=False)
+        self._compare(got, exp, slot_stride, frame_lead, per_frame=False, state=state)
         return got, exp
 
-    def lookup(self, ips, link=None):
-        found, macs = ARP.arp_lookup(self.table, [ipv4(a) for a in ips], self.d_links, link, fill=FILL)
+    def lookup(self, ips, link=None, stream=None, state=True):
+        found, macs = ARP.arp_lookup(self.table, [ipv4(a) for a in ips], self.d_links, link, stream=stream, fill=FILL)
         efound, emacs = self.model.lookup([ipv4(a) for a in ips], link)
         assert np.array_equal(found, efound) and np.array_equal(macs, emacs), (found, efound, macs, emacs)
-        self.compare_state()
+        if state:
+            self.compare_state()
         return found, macs
 
     def run(self):

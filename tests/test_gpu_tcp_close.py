@@ -9,6 +9,7 @@ import tcp_close_reference as R
 from demikernel_amd import Config, FrameBatch, RxEngine, RxResults, TcpSender, TcpTxResults
 from demikernel_amd import _native as N
 from demikernel_amd import tcp_close as TCL
+from ctl_calls import run
 
 pytestmark = pytest.mark.gpu
 
@@ -55,8 +56,13 @@ class Device:
                 bad = [c for c in range(self.nconns) if g[c].tobytes() != h[c].tobytes()]
                 raise AssertionError(f"{name} {bad[:6]} differ: got {g[bad[0]]} expected {h[bad[0]]}")
 
-    def process(self, segs, now=C.NOW, *, slot_stride=64, frame_lead=0, max_frames=None, max_done=None, out_size=None,
-                out_bytes=None, flags=0, action_in=True):
+    def process(self, segs, now=C.NOW, **kw):
+        return run(self.process_steps(segs, now, **kw))
+
+    def process_steps(self, segs, now=C.NOW, *, slot_stride=64, frame_lead=0, max_frames=None, max_done=None,
+                      out_size=None, out_bytes=None, flags=0, action_in=True, stream=None, state=True):
+        """process() in the three steps of ctl_calls.Call: the uploads and fills, the call (on `stream`), the wait and
+        the comparison. state=False leaves the tables to a later call's comparison. The same for timers and start."""
         import torch
 
         n = len(segs)
@@ -70,9 +76,11 @@ class Device:
         ain = (np.arange(n) * 7 % 13).astype(np.uint8) if action_in else None
         d_ain = up(ain) if action_in else None
         ob = d_out.numel() if out_bytes is None else out_bytes
+        yield
         TCL.close_process(r, self.d_rows, self.d_rx, self.d_tx, self.d_links, now, d_out, res, slot_stride=slot_stride,
                           frame_lead=frame_lead, flags=flags, dack=self.d_dack, action_in=d_ain, out_bytes=ob,
-                          max_frames=max_frames, max_done=max_done)
+                          max_frames=max_frames, max_done=max_done, stream=stream)
+        yield
         torch.cuda.synchronize()
         exp = self.model.process(rx, now, C.LINKS, slot_stride=slot_stride, frame_lead=frame_lead, flags=flags,
                                  max_frames=max_frames, out_bytes=ob, max_done=max_done, action_in=ain)
@@ -107,15 +115,21 @@ class Device:
             bad = np.nonzero(out != want)[0]
             raise AssertionError(f"{len(bad)} output bytes differ, first at {bad[:8]}: got {out[bad[:8]]} "
                                  f"expected {want[bad[:8]]}")
-        self.compare_state()
+        if state:
+            self.compare_state()
         return got, exp
 
-    def timers(self, now, *, max_done=None, with_tx=True):
+    def timers(self, now, **kw):
+        return run(self.timers_steps(now, **kw))
+
+    def timers_steps(self, now, *, max_done=None, with_tx=True, stream=None, state=True):
         import torch
 
         max_done = self.nconns if max_done is None else max_done
         res = TCL.CloseResults(4, 4, max_done, self.nconns, fill=FILL)
-        TCL.close_timers(self.d_rows, now, res, tx_conns=self.d_tx if with_tx else None, max_done=max_done)
+        yield
+        TCL.close_timers(self.d_rows, now, res, tx_conns=self.d_tx if with_tx else None, max_done=max_done, stream=stream)
+        yield
         torch.cuda.synchronize()
         exp = self.model.timers(now, max_done=max_done, with_tx=with_tx)
         got = res.to_numpy()
@@ -126,22 +140,30 @@ class Device:
         assert (got["done"][y:].view(np.uint8) == FILL).all()
         for k in ("action", "state_after", "ack_action", "reply_frame", "off_out", "len_out", "frame_seg", "fin_frame"):
             assert (res.raw()[k] == FILL).all(), k
-        self.compare_state()
+        if state:
+            self.compare_state()
         return got, exp
 
-    def start(self, close, fill=FILL):
+    def start(self, close, **kw):
+        return run(self.start_steps(close, **kw))
+
+    def start_steps(self, close, fill=FILL, *, stream=None, state=True):
         import torch
 
         k = len(close)
         d_close = up(np.asarray(close, np.uint32)) if k else torch.zeros(4, dtype=torch.uint8, device="cuda:0")
-        s = TCL.close_start(self.d_rows, self.d_rx, self.d_tx, d_close, nclose=k, fill=fill)
+        yield
+        s = TCL.close_start(self.d_rows, self.d_rx, self.d_tx, d_close, nclose=k, fill=fill, stream=stream)
+        yield
         torch.cuda.synchronize()
         exp = self.model.start(close)
         got = s.to_numpy()
         assert got["n_markers"] == exp["n_markers"]
         for f in ("status", "conn", "off", "len"):
             assert np.array_equal(got[f][:k], exp[f]), (f, got[f][:k], exp[f])
-        self.compare_state()
+            assert (got[f][k:].view(np.uint8) == fill).all(), f"{f} was written past its {k} entries"
+        if state:
+            self.compare_state()
         return s, exp
 
 

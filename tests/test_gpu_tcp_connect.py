@@ -13,6 +13,7 @@ import tcp_connect_reference as R
 from demikernel_amd import Config, FrameBatch, RxEngine
 from demikernel_amd import _native as N
 from demikernel_amd import tcp_connect as TC
+from ctl_calls import run
 
 pytestmark = pytest.mark.gpu
 
@@ -58,7 +59,7 @@ class Device:
         size = max(max_frames, 1) * slot_stride + 64 if out_size is None else out_size
         return torch.full((size,), CANARY, dtype=torch.uint8, device="cuda:0")
 
-    def _compare(self, got, exp, slot_stride, frame_lead, per_frame: bool):
+    def _compare(self, got, exp, slot_stride, frame_lead, per_frame: bool, state: bool = True):
         assert (got["n_frames"], got["n_ready"]) == (exp["n_frames"], exp["n_ready"])
         assert np.array_equal(got["status"], exp["status"]), (got["status"], exp["status"])
         if per_frame and exp["fits"]:
@@ -81,7 +82,8 @@ class Device:
             bad = np.nonzero(got["out"] != want)[0]
             raise AssertionError(f"{len(bad)} output bytes differ, first at {bad[:8]}: got {got['out'][bad[:8]]} "
                                  f"expected {want[bad[:8]]}")
-        self.compare_state()
+        if state:
+            self.compare_state()
 
     def compare_state(self):
         g = TC.rows_to_host(self.d_rows)
@@ -91,8 +93,13 @@ class Device:
         gen = TC.isn_gen_to_host(self.d_gen)[0]
         assert (int(gen["nonce"]), int(gen["counter"]), int(gen["reserved"])) == (self.model.nonce, self.model.counter, 0)
 
-    def start(self, start, now=C.NOW - 10, *, slot_stride=64, frame_lead=0, max_frames=None, max_ready=None, out_size=None,
-              out_bytes=None, flags=0):
+    def start(self, start, now=C.NOW - 10, **kw):
+        return run(self.start_steps(start, now, **kw))
+
+    def start_steps(self, start, now=C.NOW - 10, *, slot_stride=64, frame_lead=0, max_frames=None, max_ready=None,
+                    out_size=None, out_bytes=None, flags=0, stream=None, state=True):
+        """start() in the three steps of ctl_calls.Call: the uploads and fills, the call (on `stream`), the wait and
+        the comparison. state=False leaves the rows to a later call's comparison. The same for process and timers."""
         import torch
 
         ns = len(start)
@@ -102,19 +109,24 @@ class Device:
         res = TC.ConnectResults(4, max_frames, max_ready, ns, fill=FILL)
         d_start = TC.to_device(np.asarray(start, np.uint32)) if ns else torch.zeros(4, dtype=torch.uint8, device="cuda:0")
         ob = d_out.numel() if out_bytes is None else out_bytes
+        yield
         TC.connect_start(self.d_rows, d_start, self.d_gen, self.d_links, now, d_out, res, slot_stride=slot_stride,
                          frame_lead=frame_lead, flags=flags, nstart=ns, out_bytes=ob, max_frames=max_frames,
-                         max_ready=max_ready)
+                         max_ready=max_ready, stream=stream)
+        yield
         torch.cuda.synchronize()
         exp = self.model.start(start, now, C.LINKS, slot_stride=slot_stride, frame_lead=frame_lead, flags=flags,
                                max_frames=max_frames, out_bytes=ob, max_ready=max_ready)
         got = res.to_numpy()
         got["out"] = d_out.cpu().numpy()
-        self._compare(got, exp, slot_stride, frame_lead, per_frame=False)
+        self._compare(got, exp, slot_stride, frame_lead, per_frame=False, state=state)
         return got, exp
 
-    def process(self, frames, now=C.NOW, *, slot_stride=64, frame_lead=0, max_frames=None, max_ready=None, out_size=None,
-                out_bytes=None, flags=0, link=None):
+    def process(self, frames, now=C.NOW, **kw):
+        return run(self.process_steps(frames, now, **kw))
+
+    def process_steps(self, frames, now=C.NOW, *, slot_stride=64, frame_lead=0, max_frames=None, max_ready=None,
+                      out_size=None, out_bytes=None, flags=0, link=None, stream=None, state=True):
         import torch
 
         n = len(frames)
@@ -127,9 +139,11 @@ class Device:
         res = TC.ConnectResults(n, max_frames, max_ready, self.nrows, fill=FILL)
         d_link = None if link is None else TC.to_device(np.asarray(link, np.uint32))
         ob = d_out.numel() if out_bytes is None else out_bytes
+        yield
         TC.connect_process(rx, self.d_rows, self.d_map, self.d_links, now, d_out, res, slot_stride=slot_stride,
                            frame_lead=frame_lead, flags=flags, link=d_link, out_bytes=ob, max_frames=max_frames,
-                           max_ready=max_ready)
+                           max_ready=max_ready, stream=stream)
+        yield
         torch.cuda.synchronize()
         exp = self.model.process(before, self.cmap, now, C.LINKS, slot_stride=slot_stride, frame_lead=frame_lead,
                                  flags=flags, max_frames=max_frames, out_bytes=ob, max_ready=max_ready, link=link)
@@ -138,22 +152,28 @@ class Device:
         after = rx.to_numpy()
         for k in RX_KEYS:
             assert before[k].tobytes() == after[k].tobytes(), f"the batch's {k} was written"
-        self._compare(got, exp, slot_stride, frame_lead, per_frame=True)
+        self._compare(got, exp, slot_stride, frame_lead, per_frame=True, state=state)
         return got, exp
 
-    def timers(self, now, *, slot_stride=64, frame_lead=0, max_frames=64, max_ready=64, out_size=None, flags=0):
+    def timers(self, now, **kw):
+        return run(self.timers_steps(now, **kw))
+
+    def timers_steps(self, now, *, slot_stride=64, frame_lead=0, max_frames=64, max_ready=64, out_size=None, flags=0,
+                     stream=None, state=True):
         import torch
 
         d_out = self._out(max_frames, slot_stride, out_size)
         res = TC.ConnectResults(4, max_frames, max_ready, self.nrows, fill=FILL)
+        yield
         TC.connect_timers(self.d_rows, self.d_links, now, d_out, res, slot_stride=slot_stride, frame_lead=frame_lead,
-                          flags=flags, max_frames=max_frames, max_ready=max_ready)
+                          flags=flags, max_frames=max_frames, max_ready=max_ready, stream=stream)
+        yield
         torch.cuda.synchronize()
         exp = self.model.timers(now, C.LINKS, slot_stride=slot_stride, frame_lead=frame_lead, flags=flags,
                                 max_frames=max_frames, out_bytes=d_out.numel(), max_ready=max_ready)
         got = res.to_numpy()
         got["out"] = d_out.cpu().numpy()
-        self._compare(got, exp, slot_stride, frame_lead, per_frame=False)
+        self._compare(got, exp, slot_stride, frame_lead, per_frame=False, state=state)
         return got, exp
 
 

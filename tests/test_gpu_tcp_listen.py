@@ -15,6 +15,7 @@ from demikernel_amd import Config, FrameBatch, RxEngine
 from demikernel_amd import _native as N
 from demikernel_amd import tcp_listen as TL
 from demikernel_amd.rx import Fail
+from ctl_calls import run
 
 pytestmark = pytest.mark.gpu
 
@@ -59,9 +60,16 @@ class Device:
         size = max(max_frames, 1) * slot_stride + 64 if out_size is None else out_size
         return torch.full((size,), CANARY, dtype=torch.uint8, device="cuda:0")
 
-    def process(self, frames, now=C.NOW, *, slot_stride=64, frame_lead=0, max_frames=None, max_ready=None,
-                out_size=None, out_bytes=None, flags=0, link=None, compare=True):
+    def process(self, frames, now=C.NOW, **kw):
         """One dk_tcp_listen_process call on `frames`, compared whole with the model's."""
+        return run(self.process_steps(frames, now, **kw))
+
+    def process_steps(self, frames, now=C.NOW, *, slot_stride=64, frame_lead=0, max_frames=None, max_ready=None,
+                      out_size=None, out_bytes=None, flags=0, link=None, compare=True, stream=None, state=True,
+                      released=()):
+        """process() in the three steps of ctl_calls.Call: the uploads and fills, the call (on `stream`), the wait and
+        the comparison. state=False leaves the tables to a later call's comparison; `released` are keys a later call
+        has taken out of the table by then."""
         import torch
 
         n = len(frames)
@@ -74,9 +82,11 @@ class Device:
         res = TL.ListenResults(n, max_frames, max_ready, self.nl, fill=FILL)
         d_link = None if link is None else TL.to_device(np.asarray(link, np.uint32))
         ob = d_out.numel() if out_bytes is None else out_bytes
+        yield
         TL.listen_process(self.table, rx, self.d_L, self.d_lsn, self.d_links, now, d_out, res, slot_stride=slot_stride,
                           frame_lead=frame_lead, flags=flags, backlog_sum=self.backlog_sum, link=d_link, out_bytes=ob,
-                          max_frames=max_frames, max_ready=max_ready)
+                          max_frames=max_frames, max_ready=max_ready, stream=stream)
+        yield
         torch.cuda.synchronize()
         exp = self.model.process(before, self.lsn, now, C.LINKS, slot_stride=slot_stride, frame_lead=frame_lead,
                                  flags=flags, max_frames=max_frames, out_bytes=ob, max_ready=max_ready, link=link)
@@ -86,11 +96,12 @@ class Device:
         for k in RX_KEYS + ("tcp_opts",):
             assert before[k].tobytes() == after[k].tobytes(), f"the batch's {k} was written"
         if compare:
-            self.compare_process(got, exp, n, max_frames, max_ready, slot_stride, frame_lead)
-            self.compare_state()
+            self.compare_process(got, exp, n, max_frames, max_ready, slot_stride, frame_lead, released)
+            if state:
+                self.compare_state()
         return got, exp
 
-    def compare_process(self, got, exp, n, max_frames, max_ready, slot_stride, frame_lead):
+    def compare_process(self, got, exp, n, max_frames, max_ready, slot_stride, frame_lead, released=()):
         assert (got["n_frames"], got["n_ready"]) == (exp["n_frames"], exp["n_ready"])
         assert np.array_equal(got["status"], exp["status"]), (got["status"], exp["status"])
         rows = self.table.rows()
@@ -106,6 +117,8 @@ class Device:
                 k = exp["keys"][i]
                 if k is None:
                     assert got["slot"][i] == TL.NONE, i
+                elif k in released:
+                    assert int(rows[got["slot"][i]]["key"]) == TL.KEY_TOMBSTONE, i
                 else:
                     assert got["slot"][i] < len(rows) and int(rows[got["slot"][i]]["key"]) == k, (i, TL.ACTIONS[exp["action"][i]])
             w, y = exp["n_frames"], exp["n_ready"]
@@ -114,7 +127,8 @@ class Device:
             assert np.array_equal(got["frame_seg"][:w], np.array(exp["frame_seg"], np.uint32))
             for j in range(y):
                 g, e = got["ready"][j].copy(), exp["ready"][j].copy()
-                assert int(rows[g["slot"]]["key"]) == exp["ready_keys"][j], j
+                want_key = TL.KEY_TOMBSTONE if exp["ready_keys"][j] in released else exp["ready_keys"][j]
+                assert int(rows[g["slot"]]["key"]) == want_key, j
                 g["slot"] = e["slot"] = 0
                 assert g.tobytes() == e.tobytes(), (j, g, e)
         assert (got["off_out"][w:] == FILL32).all() and (got["len_out"][w:] == FILL16).all()
@@ -143,14 +157,20 @@ class Device:
         gl = TL.listeners_to_host(self.d_L)
         assert gl.tobytes() == self.model.listeners.tobytes(), [(a, b) for a, b in zip(gl, self.model.listeners) if a != b][:2]
 
-    def timers(self, now, *, slot_stride=64, frame_lead=0, max_frames=64, max_ready=64, out_size=None, flags=0):
+    def timers(self, now, **kw):
+        return run(self.timers_steps(now, **kw))
+
+    def timers_steps(self, now, *, slot_stride=64, frame_lead=0, max_frames=64, max_ready=64, out_size=None, flags=0,
+                     stream=None):
         import torch
 
         d_out = self._out(max_frames, slot_stride, out_size)
         res = TL.ListenResults(0, max_frames, max_ready, self.nl, fill=FILL)
+        yield
         TL.listen_timers(self.table, self.d_L, self.d_links, now, d_out, res, slot_stride=slot_stride,
                          frame_lead=frame_lead, flags=flags, backlog_sum=self.backlog_sum, max_frames=max_frames,
-                         max_ready=max_ready)
+                         max_ready=max_ready, stream=stream)
+        yield
         torch.cuda.synchronize()
         exp = self.model.timers(now, C.LINKS, slot_stride=slot_stride, frame_lead=frame_lead, flags=flags,
                                 max_frames=max_frames, out_bytes=d_out.numel(), max_ready=max_ready)
@@ -181,8 +201,8 @@ class Device:
         self.compare_state()
         return got, exp, gf
 
-    def release(self, keys):
-        found = TL.listen_release(self.table, self.d_L, keys)
+    def release(self, keys, stream=None):
+        found = TL.listen_release(self.table, self.d_L, keys, stream=stream)
         assert [int(x) for x in found] == self.model.release(keys)
         self.compare_state()
         return found
