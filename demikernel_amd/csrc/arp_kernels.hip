@@ -562,10 +562,10 @@ int dk_arp_table_create(int32_t device, uint32_t cap, const dk_arp_cfg* cfg, dk_
 void dk_arp_table_destroy(dk_arp_table* t) {
     if (!t) return;
     dk::ctl::DeviceGuard g(t->device);
-    if (t->call.used) (void)hipEventSynchronize(t->call.last);
+    (void)t->call.drain();
     if (t->slots) (void)hipFree(t->slots);
     if (t->consumed) (void)hipFree(t->consumed);
-    if (t->call.scratch) (void)hipFree(t->call.scratch);
+    t->call.scratch.free();
     if (t->call.last) (void)hipEventDestroy(t->call.last);
     delete t;
 }
@@ -575,7 +575,7 @@ int dk_arp_table_stats(dk_arp_table* t, uint32_t* cap, uint64_t* consumed) {
     dk::ctl::DeviceGuard g(t->device);
     if (cap) *cap = t->cap;
     if (consumed) {
-        if (t->call.used && hipEventSynchronize(t->call.last) != hipSuccess) return EIO;
+        if (t->call.drain()) return EIO;
         if (hipMemcpy(consumed, t->consumed, sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess) return EIO;
     }
     return 0;
@@ -584,14 +584,14 @@ int dk_arp_table_stats(dk_arp_table* t, uint32_t* cap, uint64_t* consumed) {
 int dk_arp_table_read(dk_arp_table* t, dk_arp_slot* rows) {
     if (!t || !rows) return EINVAL;
     dk::ctl::DeviceGuard g(t->device);
-    if (t->call.used && hipEventSynchronize(t->call.last) != hipSuccess) return EIO;
+    if (t->call.drain()) return EIO;
     return hipMemcpy(rows, t->slots, (size_t)t->cap * sizeof(dk_arp_slot), hipMemcpyDeviceToHost) == hipSuccess ? 0 : EIO;
 }
 
 int dk_arp_table_write(dk_arp_table* t, const dk_arp_slot* rows) {
     if (!t || !rows) return EINVAL;
     dk::ctl::DeviceGuard g(t->device);
-    if (t->call.used && hipEventSynchronize(t->call.last) != hipSuccess) return EIO;
+    if (t->call.drain()) return EIO;
     uint64_t consumed = 0;
     for (uint32_t s = 0; s < t->cap; s++) {
         if (rows[s].state > DK_ARP_SLOT_TOMBSTONE) return EINVAL;
@@ -650,7 +650,7 @@ int dk_arp_process(dk_arp_table* t, const dk_rx_batch* batch, const dk_rx_result
     fill_common(P, t, rows, nrows, links, nlinks, out, out_bytes, layout, max_frames, max_ready, res);
     P.frames = batch->frames, P.frames_bytes = batch->frames_bytes, P.off = batch->off;
     P.meta = rx->meta, P.src = rx->src_ip, P.dst = rx->dst_ip, P.n = n, P.clock = clock_ns, P.hcap = hcap;
-    Carver c{static_cast<uint8_t*>(t->call.scratch)};
+    Carver c{t->call.scratch.p};
     P.hL = c.take<uint32_t>(hcap);
     P.hfirst = c.take<uint32_t>(hcap);
     P.hts = c.take<uint32_t>(hcap);
@@ -714,7 +714,7 @@ int dk_arp_query_start(dk_arp_table* t, dk_arp_query* rows, uint32_t nrows, cons
     Params P{};
     fill_common(P, t, rows, nrows, links, nlinks, out, out_bytes, layout, max_frames, max_ready, res);
     P.start = start, P.nstart = nstart, P.now = now_ns;
-    Carver c{static_cast<uint8_t*>(t->call.scratch)};
+    Carver c{t->call.scratch.p};
     P.term = c.take<uint32_t>(nrows);
     P.f0 = c.take<uint32_t>(1);
     P.tot = c.take<uint64_t>(kTots);
@@ -757,7 +757,7 @@ int dk_arp_timers(dk_arp_table* t, dk_arp_query* rows, uint32_t nrows, dk_tx_lin
     Params P{};
     fill_common(P, t, rows, nrows, links, nlinks, out, out_bytes, layout, max_frames, max_ready, res);
     P.now = now_ns;
-    Carver c{static_cast<uint8_t*>(t->call.scratch)};
+    Carver c{t->call.scratch.p};
     P.f0 = c.take<uint32_t>(1);
     P.tot = c.take<uint64_t>(kTots);
     P.keep = c.take<uint8_t>(t->cap);

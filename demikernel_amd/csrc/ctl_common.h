@@ -1,11 +1,19 @@
-// ctl_common.h — what the control-plane kernel files (tcp_listen, tcp_connect, tcp_close, arp) share.
+// ctl_common.h — what the kernel files share beyond rx_common.h: the control-plane families (tcp_listen, tcp_connect,
+// tcp_close, arp) all of it, the TCP data-plane contexts (tcp_kernels, tcp_tx, tcp_ack, tcp_ackemit, tcp_cc, tcp_commit)
+// the call scaffold of (b).
 //   (a) No HIP needed (DK_HD): the checksum helpers, the ISN generator's CRC and the one builder of a TCP frame with no
 //       payload. tests/host_asan compiles this part with a host compiler under ASan + UBSan.
-//   (b) HIP only: the agent-scope atomic wrappers, scratch carving, the launch grid, the device guard, and CallScratch,
-//       the scratch buffer and event that order a family's calls on one device.
+//   (b) HIP only: the agent-scope atomic wrappers, scratch carving, the launch grid, the device guard, and the call
+//       scaffold: CallOrder, the event that serialises an owner's calls on one device; Buf<T>, a device buffer that
+//       waits for that order before it frees; CallScratch, the two together for an owner with one byte scratch.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
+#if defined(__HIPCC__)
+#include <errno.h>
+
+#include <algorithm>
+#endif
 
 #include "rx_common.h"
 
@@ -93,10 +101,6 @@ DK_HD void tcp_frame(uint8_t* a, const dk_tx_link* lk, uint32_t ipw, uint32_t sr
 }
 
 #if defined(__HIPCC__)
-#include <errno.h>
-
-#include <algorithm>
-
 // ---- (b) ----------------------------------------------------------------------------------------------------------------
 constexpr uint32_t kBlock = 256, kWave = 64;
 constexpr int kMaxDevices = 64;
@@ -140,25 +144,18 @@ struct DeviceGuard {
     }
 };
 
-// The scratch of a family's calls on one device, and the event that serialises them on it. `last` is the owner's to
-// create, before the first record().
-struct CallScratch {
-    void* scratch = nullptr;
-    size_t cap = 0;
+// CallOrder, Buf and free_all are internal to the kernel files: hidden, so their inline and template instances are no
+// part of the library's symbol list.
+#pragma GCC visibility push(hidden)
+
+// The order of an owner's calls (a context's, a table's, a pool entry's) on one device: each call's stream is put behind
+// the call before it, so two streams never overlap on the owner's buffers. `last` is the owner's to create, before the
+// first record().
+struct CallOrder {
     hipEvent_t last = nullptr;
     hipStream_t last_stream = nullptr;
     bool used = false;
 
-    // The scratch grown to `need` bytes; waits for in-flight work on the old one first.
-    int grow(size_t need) {
-        if (cap >= need) return 0;
-        if (used && hipEventSynchronize(last) != hipSuccess) return EIO;
-        if (scratch) (void)hipFree(scratch);
-        scratch = nullptr, cap = 0;
-        if (hipMalloc(&scratch, need) != hipSuccess) return ENOMEM;
-        cap = need;
-        return 0;
-    }
     // Stream s ordered behind the last call.
     int order(hipStream_t s) {
         return used && last_stream != s && hipStreamWaitEvent(s, last, 0) != hipSuccess ? EIO : 0;
@@ -171,6 +168,44 @@ struct CallScratch {
         used = true;
         return 0;
     }
+    // The host waits for the last call, if there was one: before a buffer is freed, a table is read, the owner destroyed.
+    int drain() { return used && hipEventSynchronize(last) != hipSuccess ? EIO : 0; }
+};
+
+// A device buffer of `cap` elements that only grows. Every buffer it frees was waited for: no list of the buffers a
+// call is about to grow has to be kept in step with the calls that use them. A first allocation frees nothing and
+// waits for nothing.
+template <class T>
+struct Buf {
+    T* p = nullptr;
+    size_t cap = 0;
+
+    // At least n elements; drains `o` before the old ones go. EIO, ENOMEM.
+    int grow(CallOrder& o, size_t n) {
+        if (cap >= n) return 0;
+        if (p && o.drain()) return EIO;
+        free();
+        if (hipMalloc(reinterpret_cast<void**>(&p), n * sizeof(T)) != hipSuccess) return ENOMEM;
+        cap = n;
+        return 0;
+    }
+    void free() {
+        if (p) (void)hipFree(p);
+        p = nullptr, cap = 0;
+    }
+};
+
+template <class... B>
+void free_all(B&... b) {
+    (b.free(), ...);
+}
+
+#pragma GCC visibility pop
+
+// An owner with one byte scratch, carved anew by every call (Carver).
+struct CallScratch : CallOrder {
+    Buf<uint8_t> scratch;
+    int grow(size_t need) { return scratch.grow(*this, need); }
 };
 
 // For the families that keep no table: the current device's entry of `pools` (its event made on first use) with at

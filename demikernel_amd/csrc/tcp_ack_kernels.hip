@@ -508,16 +508,7 @@ __global__ __launch_bounds__(kWave) void dk_tcp_ack_finish_kernel(Params P) {
     finish_wave(P, c, k0, r0, r1, serial, cs.x, upd, useq, uack, uwin, new_acks, dup_acks, scan_l);
 }
 
-struct DeviceGuard {
-    int prev = -1;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) (void)hipSetDevice(dev);
-    }
-    ~DeviceGuard() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
+using dk::ctl::DeviceGuard;
 
 }  // namespace
 }  // namespace dk_tcp_ack
@@ -556,7 +547,7 @@ int dk_tcp_ack_process(dk_tcp_ctx* t, const dk_rx_results* rx, uint32_t n, const
     if (n == 0 && nconns == 0) return 0;
     DeviceGuard g(o.device);
     const hipStream_t s = (hipStream_t)stream;
-    if (*o.used && *o.last_stream != s && hipStreamWaitEvent(s, o.last, 0) != hipSuccess) return EINVAL;
+    if (o.serial->order(s)) return EINVAL;
     if (n && hipMemsetAsync(out->acked, 0, (size_t)n * sizeof(uint32_t), s) != hipSuccess) return EINVAL;
     if (nconns) {
         Params P{};
@@ -581,14 +572,8 @@ int dk_tcp_ack_process(dk_tcp_ctx* t, const dk_rx_results* rx, uint32_t n, const
         if (form == 2) {
             const size_t slots = (size_t)n / kWave + nconns + 1;
             const size_t need = slots * (sizeof(uint4) + sizeof(uint2) + 2 * sizeof(int)) + (size_t)nconns * sizeof(int2);
-            if (o.ack->scratch_cap < need) {
-                if (*o.used && hipEventSynchronize(o.last) != hipSuccess) return EINVAL;  // in-flight work on it
-                if (o.ack->scratch) (void)hipFree(o.ack->scratch);
-                o.ack->scratch = nullptr, o.ack->scratch_cap = 0;
-                if (hipMalloc(&o.ack->scratch, need) != hipSuccess) return ENOMEM;
-                o.ack->scratch_cap = need;
-            }
-            uint8_t* b = static_cast<uint8_t*>(o.ack->scratch);
+            if (int rc = o.ack->scratch.grow(*o.serial, need)) return rc == EIO ? EINVAL : rc;
+            uint8_t* b = o.ack->scratch.p;
             P.wpart = reinterpret_cast<uint4*>(b), b += slots * sizeof(uint4);
             P.wcnt = reinterpret_cast<uint2*>(b), b += slots * sizeof(uint2);
             P.cstate = reinterpret_cast<int2*>(b), b += (size_t)nconns * sizeof(int2);
@@ -608,12 +593,8 @@ int dk_tcp_ack_process(dk_tcp_ctx* t, const dk_rx_results* rx, uint32_t n, const
         else
             hipLaunchKernelGGL(dk_tcp_ack_lane_kernel, dim3((nconns + kLaneBlock - 1) / kLaneBlock), dim3(kLaneBlock), 0,
                                s, P);
-        if (hipGetLastError() != hipSuccess) return EINVAL;
     }
-    if (hipEventRecord(o.last, s) != hipSuccess) return EINVAL;
-    *o.last_stream = s;
-    *o.used = true;
-    return 0;
+    return o.serial->record(s) ? EINVAL : 0;
 }
 
 }  // extern "C"

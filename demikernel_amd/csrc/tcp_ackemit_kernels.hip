@@ -367,17 +367,7 @@ __global__ __launch_bounds__(kBlock) void ackemit_finish_kernel(Params P) {
     }
 }
 
-struct DeviceGuard {
-    int prev = -1;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) (void)hipSetDevice(dev);
-    }
-    ~DeviceGuard() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
+using dk::ctl::DeviceGuard;
 using dk::ctl::round16;
 
 }  // namespace
@@ -420,38 +410,27 @@ int dk_tcp_ack_emit(dk_tcp_ctx* t, const dk_rx_results* rx, uint32_t n, const ui
     const uint32_t nb = (n + kTile - 1) / kTile, sb = dk_tcp_tx_scan_tiles(n);
     const size_t need = 3 * round16((size_t)n * 4) + 2 * round16((size_t)n * 8) + round16((size_t)sb * 8) +
                         round16((size_t)nb * 4) + round16((size_t)nb * 8) + round16((size_t)nconns * 4) + 16;
-    if (o.emit->scratch_cap < need) {
-        if (*o.used && hipEventSynchronize(o.last) != hipSuccess) return EIO;  // in-flight work on it
-        if (o.emit->scratch) (void)hipFree(o.emit->scratch);
-        o.emit->scratch = nullptr, o.emit->scratch_cap = 0;
-        if (hipMalloc(&o.emit->scratch, need) != hipSuccess) return ENOMEM;
-        o.emit->scratch_cap = need;
-    }
+    if (int rc = o.emit->scratch.grow(*o.serial, need)) return rc;
     o.emit->done = o.call;
     o.emit->last_form = -1;
-    if (*o.used && *o.last_stream != s && hipStreamWaitEvent(s, o.last, 0) != hipSuccess) return EIO;
+    if (o.serial->order(s)) return EIO;
     Params P{};
     P.svals = o.svals, P.range = o.range, P.rec = o.rec;
     P.action = action, P.view = view, P.rx = rx_conns, P.tx = tx_conns, P.dack = dack;
     P.n = n, P.nconns = nconns, P.nlinks = nlinks;
     P.stride = layout->slot_stride, P.lead = layout->frame_lead, P.max_frames = max_frames;
     P.out_bytes = out_bytes, P.now = now_ns;
-    uint8_t* b = static_cast<uint8_t*>(o.emit->scratch);
-    const auto take = [&](size_t bytes) {
-        uint8_t* p = b;
-        b += round16(bytes);
-        return p;
-    };
-    P.flag = reinterpret_cast<uint64_t*>(take((size_t)n * 8));
-    P.esum = reinterpret_cast<uint64_t*>(take((size_t)n * 8));
-    uint64_t* bsum = reinterpret_cast<uint64_t*>(take((size_t)sb * 8));
-    P.tile_v = reinterpret_cast<uint64_t*>(take((size_t)nb * 8));
-    P.tot = reinterpret_cast<uint64_t*>(take(8));
-    P.morder = reinterpret_cast<uint32_t*>(take((size_t)n * 4));
-    P.mconn = reinterpret_cast<uint32_t*>(take((size_t)n * 4));
-    P.ackno = reinterpret_cast<uint32_t*>(take((size_t)n * 4));
-    P.tile_m = reinterpret_cast<uint32_t*>(take((size_t)nb * 4));
-    P.pend = reinterpret_cast<uint32_t*>(take((size_t)nconns * 4));
+    dk::ctl::Carver c{o.emit->scratch.p};
+    P.flag = c.take<uint64_t>(n);
+    P.esum = c.take<uint64_t>(n);
+    uint64_t* bsum = c.take<uint64_t>(sb);
+    P.tile_v = c.take<uint64_t>(nb);
+    P.tot = c.take<uint64_t>(1);
+    P.morder = c.take<uint32_t>(n);
+    P.mconn = c.take<uint32_t>(n);
+    P.ackno = c.take<uint32_t>(n);
+    P.tile_m = c.take<uint32_t>(nb);
+    P.pend = c.take<uint32_t>(nconns);
     P.res = *res;
     const dim3 per_conn((nconns + kBlock - 1) / kBlock), per_frame((n + kBlock - 1) / kBlock);
     if (nconns) hipLaunchKernelGGL(ackemit_conn_kernel, per_conn, dim3(kBlock), 0, s, P);
@@ -480,11 +459,7 @@ int dk_tcp_ack_emit(dk_tcp_ctx* t, const dk_rx_results* rx, uint32_t n, const ui
         if (max_frames && dk_launch_tcp_ack_emit(E, grid, s)) return EIO;
         hipLaunchKernelGGL(ackemit_finish_kernel, dim3((std::max(n, nconns) + kBlock - 1) / kBlock), dim3(kBlock), 0, s, P);
     }
-    if (hipGetLastError() != hipSuccess) return EIO;
-    if (hipEventRecord(o.last, s) != hipSuccess) return EIO;
-    *o.last_stream = s;
-    *o.used = true;
-    return 0;
+    return o.serial->record(s);
 }
 
 }  // extern "C"

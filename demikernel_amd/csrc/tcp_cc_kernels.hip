@@ -359,16 +359,7 @@ __global__ __launch_bounds__(256) void dk_tcp_cc_cbrt_kernel(const float* in, fl
     if (i < n) out[i] = dk_cc::cbrt_f32(in[i]);
 }
 
-struct DeviceGuard {
-    int prev = -1;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) (void)hipSetDevice(dev);
-    }
-    ~DeviceGuard() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
+using dk::ctl::DeviceGuard;
 
 bool misaligned(const void* a, const void* b, const void* c, const void* d = nullptr) {
     return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c) |
@@ -406,18 +397,14 @@ int dk_tcp_cc_ack(dk_tcp_ctx* t, const dk_rx_results* rx, uint32_t n, const uint
     if (n == 0 && nconns == 0) return 0;
     DeviceGuard g(o.device);
     const hipStream_t s = (hipStream_t)stream;
-    if (*o.used && *o.last_stream != s && hipStreamWaitEvent(s, o.last, 0) != hipSuccess) return EIO;
+    if (o.serial->order(s)) return EIO;
     if (n && out->cwnd_after && hipMemsetAsync(out->cwnd_after, 0, (size_t)n * sizeof(uint32_t), s) != hipSuccess)
         return EIO;
     if (nconns) {
         AckParams P{o.svals, o.range, o.rec, action, rx_conns, tx_conns, ack_conns, cc, nconns, now_ns, *out};
         hipLaunchKernelGGL(dk_tcp_cc_ack_kernel, dim3((nconns + kBlock - 1) / kBlock), dim3(kBlock), 0, s, P);
-        if (hipGetLastError() != hipSuccess) return EIO;
     }
-    if (hipEventRecord(o.last, s) != hipSuccess) return EIO;
-    *o.last_stream = s;
-    *o.used = true;
-    return 0;
+    return o.serial->record(s);
 }
 
 int dk_tcp_timers(dk_tcp_tx_ctx* t, dk_tcp_tx_conn* tx_conns, const dk_tcp_ack_conn* ack_conns, dk_tcp_cc_conn* cc,
@@ -431,7 +418,7 @@ int dk_tcp_timers(dk_tcp_tx_ctx* t, dk_tcp_tx_conn* tx_conns, const dk_tcp_ack_c
     if (misaligned(tx_conns, ack_conns, cc, dack)) return EINVAL;
     DeviceGuard g(o.device);
     const hipStream_t s = (hipStream_t)stream;
-    if (*o.used && *o.last_stream != s && hipStreamWaitEvent(s, o.last, 0) != hipSuccess) return EIO;
+    if (o.serial->order(s)) return EIO;
     if (hipMemsetAsync(out->n_fast, 0, sizeof(uint32_t), s) != hipSuccess ||
         hipMemsetAsync(out->n_timeout, 0, sizeof(uint32_t), s) != hipSuccess ||
         hipMemsetAsync(out->n_ack, 0, sizeof(uint32_t), s) != hipSuccess)
@@ -439,12 +426,8 @@ int dk_tcp_timers(dk_tcp_tx_ctx* t, dk_tcp_tx_conn* tx_conns, const dk_tcp_ack_c
     if (nconns) {
         TimerParams P{tx_conns, ack_conns, cc, dack, nconns, now_ns, rtx_fire, ack_fire, *out};
         hipLaunchKernelGGL(dk_tcp_timers_kernel, dim3((nconns + kBlock - 1) / kBlock), dim3(kBlock), 0, s, P);
-        if (hipGetLastError() != hipSuccess) return EIO;
     }
-    if (hipEventRecord(o.last, s) != hipSuccess) return EIO;
-    *o.last_stream = s;
-    *o.used = true;
-    return 0;
+    return o.serial->record(s);
 }
 
 int dk_tcp_cc_send(dk_tcp_tx_ctx* t, uint32_t phase, dk_tcp_tx_conn* tx_conns, const dk_tcp_ack_conn* ack_conns,
@@ -462,17 +445,13 @@ int dk_tcp_cc_send(dk_tcp_tx_ctx* t, uint32_t phase, dk_tcp_tx_conn* tx_conns, c
         return EINVAL;
     DeviceGuard g(o.device);
     const hipStream_t s = (hipStream_t)stream;
-    if (*o.used && *o.last_stream != s && hipStreamWaitEvent(s, o.last, 0) != hipSuccess) return EIO;
+    if (o.serial->order(s)) return EIO;
     if (nconns) {
         SendParams P{tx_conns, ack_conns, cc, nconns, after ? nbufs : 0u, phase, now_ns, {}, {}, status};
         if (after && nbufs) P.push = *push, P.res = *res;
         hipLaunchKernelGGL(dk_tcp_cc_send_kernel, dim3((nconns + kBlock - 1) / kBlock), dim3(kBlock), 0, s, P);
-        if (hipGetLastError() != hipSuccess) return EIO;
     }
-    if (hipEventRecord(o.last, s) != hipSuccess) return EIO;
-    *o.last_stream = s;
-    *o.used = true;
-    return 0;
+    return o.serial->record(s);
 }
 
 }  // extern "C"

@@ -426,7 +426,7 @@ int dk_tcp_close_start(dk_tcp_closer* rows, dk_tcp_conn* rx_conns, const dk_tcp_
     P.rows = rows, P.rxc = rx_conns, P.txc = tx_conns, P.nconns = nconns;
     P.close = close, P.nclose = nclose, P.st_status = status;
     P.push_conn = push_conn, P.push_off = push_off, P.push_len = push_len, P.n_markers = n_markers;
-    Carver c{static_cast<uint8_t*>(pool->scratch)};
+    Carver c{pool->scratch.p};
     P.tot = c.take<uint64_t>(2);
     P.flag_r = c.take<uint64_t>(nclose);
     P.pmax = c.take<uint64_t>(nclose);
@@ -470,7 +470,7 @@ int dk_tcp_close_process(const dk_rx_results* rx, uint32_t n, dk_tcp_closer* row
     P.action_in = action_in, P.links = links, P.nlinks = nlinks, P.now = now_ns;
     P.out = out, P.out_bytes = out_bytes, P.stride = layout->slot_stride, P.lead = layout->frame_lead;
     P.max_frames = max_frames, P.max_done = max_done, P.flags = flags, P.res = *res;
-    Carver c{static_cast<uint8_t*>(pool->scratch)};
+    Carver c{pool->scratch.p};
     P.t1 = c.take<uint32_t>(nconns);
     P.t2 = c.take<uint32_t>(nconns);
     uint8_t* zz = c.b;
@@ -516,7 +516,7 @@ int dk_tcp_close_timers(dk_tcp_closer* rows, dk_tcp_tx_conn* tx_conns, uint32_t 
     Params P{};
     P.rows = rows, P.txw = tx_conns, P.nconns = nconns, P.now = now_ns, P.max_done = max_done;
     P.res.done = done, P.res.n_done = n_done, P.st_status = status;
-    Carver c{static_cast<uint8_t*>(pool->scratch)};
+    Carver c{pool->scratch.p};
     P.tot = c.take<uint64_t>(2);
     P.work = c.take<uint32_t>(nconns);
     P.flag_y = c.take<uint64_t>(nconns);

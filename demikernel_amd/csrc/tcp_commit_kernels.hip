@@ -163,16 +163,7 @@ __global__ __launch_bounds__(kBlock) void dk_tcp_rtx_piggyback_kernel(const uint
     if (c < nconns && status[c] == DK_TCP_RTX_SENT) dack[c].armed = 0;
 }
 
-struct DeviceGuard {
-    int prev = -1;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) (void)hipSetDevice(dev);
-    }
-    ~DeviceGuard() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
+using dk::ctl::DeviceGuard;
 
 bool misaligned(const void* a, const void* b) {
     return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15) != 0;
@@ -222,18 +213,11 @@ int dk_tcp_tx_commit(dk_tcp_tx_ctx* t, const dk_tcp_tx_push* push, uint32_t nbuf
     }
     DeviceGuard g(o.device);
     const hipStream_t s = (hipStream_t)stream;
-    if (form == 1 && st.scratch_cap < nconns) {
-        if (*o.used && hipEventSynchronize(o.last) != hipSuccess) return EIO;  // in-flight work on the scratch
-        if (st.scratch) (void)hipFree(st.scratch);
-        st.scratch = nullptr;
-        st.scratch_cap = 0;
-        if (hipMalloc(&st.scratch, (size_t)nconns * sizeof(uint2)) != hipSuccess) return ENOMEM;
-        st.scratch_cap = nconns;
-    }
+    if (form == 1)
+        if (int rc = st.scratch.grow(*o.serial, nconns)) return rc;
     st.done = st.seg_call;
-    if (*o.used && *o.last_stream != s && hipStreamWaitEvent(s, o.last, 0) != hipSuccess) return EIO;
-    Params P{{}, {}, nbufs, max_frames, ack_conns, nconns, *q, q_cap, dack, now_ns, *out,
-             static_cast<uint2*>(st.scratch)};
+    if (o.serial->order(s)) return EIO;
+    Params P{{}, {}, nbufs, max_frames, ack_conns, nconns, *q, q_cap, dack, now_ns, *out, st.scratch.p};
     if (nbufs) P.push = *push, P.res = *res;
     const dim3 per_conn((nconns + kWaves - 1) / kWaves);
     if (form == 1) {
@@ -245,10 +229,7 @@ int dk_tcp_tx_commit(dk_tcp_tx_ctx* t, const dk_tcp_tx_push* push, uint32_t nbuf
     }
     if (hipGetLastError() != hipSuccess) return EIO;
     st.last_form = form;
-    if (hipEventRecord(o.last, s) != hipSuccess) return EIO;
-    *o.last_stream = s;
-    *o.used = true;
-    return 0;
+    return o.serial->record(s);
 }
 
 int dk_tcp_rtx_piggyback(dk_tcp_tx_ctx* t, const dk_tcp_rtx_results* res, dk_tcp_dack_conn* dack, uint32_t nconns,
@@ -261,14 +242,10 @@ int dk_tcp_rtx_piggyback(dk_tcp_tx_ctx* t, const dk_tcp_rtx_results* res, dk_tcp
     if (nconns == 0) return 0;
     DeviceGuard g(o.device);
     const hipStream_t s = (hipStream_t)stream;
-    if (*o.used && *o.last_stream != s && hipStreamWaitEvent(s, o.last, 0) != hipSuccess) return EIO;
+    if (o.serial->order(s)) return EIO;
     hipLaunchKernelGGL(dk_tcp_rtx_piggyback_kernel, dim3((nconns + kBlock - 1) / kBlock), dim3(kBlock), 0, s, res->status,
                        dack, nconns);
-    if (hipGetLastError() != hipSuccess) return EIO;
-    if (hipEventRecord(o.last, s) != hipSuccess) return EIO;
-    *o.last_stream = s;
-    *o.used = true;
-    return 0;
+    return o.serial->record(s);
 }
 
 }  // extern "C"

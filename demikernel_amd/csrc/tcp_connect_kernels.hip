@@ -452,7 +452,7 @@ int dk_tcp_connect_start(dk_tcp_connector* rows, uint32_t nrows, const uint32_t*
     Params P{};
     fill_common(P, rows, nrows, links, nlinks, now_ns, out, out_bytes, layout, max_frames, max_ready, flags, res);
     P.start = start, P.nstart = nstart, P.gen = isn_gen;
-    Carver c{static_cast<uint8_t*>(pool->scratch)};
+    Carver c{pool->scratch.p};
     P.term = c.take<uint32_t>(nrows);
     P.tot = c.take<uint64_t>(3);
     P.flag_r = c.take<uint64_t>(nstart);
@@ -497,7 +497,7 @@ int dk_tcp_connect_process(const dk_rx_results* rx, uint32_t n, dk_tcp_connector
     Params P{};
     fill_common(P, rows, nrows, links, nlinks, now_ns, out, out_bytes, layout, max_frames, max_ready, flags, res);
     P.rx = *rx, P.n = n, P.conn_of_flow = conn_of_flow, P.nflows = nflows, P.link = link;
-    Carver c{static_cast<uint8_t*>(pool->scratch)};
+    Carver c{pool->scratch.p};
     P.term = c.take<uint32_t>(nrows);
     P.first = c.take<uint32_t>(nrows);
     P.head = c.take<uint32_t>(nrows);
@@ -562,7 +562,7 @@ int dk_tcp_connect_timers(dk_tcp_connector* rows, uint32_t nrows, const dk_tx_li
     if (int rc = enter_pool(g_pool, need, s, &pool)) return rc;
     Params P{};
     fill_common(P, rows, nrows, links, nlinks, now_ns, out, out_bytes, layout, max_frames, max_ready, flags, res);
-    Carver c{static_cast<uint8_t*>(pool->scratch)};
+    Carver c{pool->scratch.p};
     P.tot = c.take<uint64_t>(3);
     P.work = c.take<uint32_t>(nrows);
     P.flag_r = c.take<uint64_t>(nrows);

@@ -1708,56 +1708,28 @@ Walker pick_walk(uint32_t n, uint32_t nconns, int force, bool reordered) {
     return kWaveWalk;
 }
 
-struct DeviceGuard {
-    int prev = -1;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) (void)hipSetDevice(dev);
-    }
-    ~DeviceGuard() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
-template <class T>
-int grow(T*& p, size_t& cap, size_t n) {
-    if (cap >= n) return 0;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    if (hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess) return ENOMEM;
-    cap = n;
-    return 0;
-}
+using dk::ctl::DeviceGuard;
 
 }  // namespace
 }  // namespace dk_tcp
 
 // One scratch set per context (sort keys, sorted pairs, records, ranges, sort temp). Calls are ordered on their
-// streams; a call on a different stream than the previous one first waits for the previous call's work (`last`), so
-// two streams never overlap on the scratch, and growing it waits for that work before freeing.
+// streams; a call on a different stream than the previous one first waits for the previous call's work (`serial`), so
+// two streams never overlap on the scratch, and a buffer that grows waits for that work before it is freed.
 struct dk_tcp_ctx {
     int device = 0;
     int walk = -1;  // dk_diag_tcp_set_walk: 0 lane, 1 wave, 2 relay, 3 scan, -1 the engine's rule
     int relay_waves = 8;  // dk_diag_tcp_set_walk (4 / 8 / 16; 8 measured best, session r05r)
-    hipEvent_t last = nullptr;
-    hipStream_t last_stream = nullptr;
-    bool used = false;
-    uint32_t *keys = nullptr, *skeys = nullptr, *svals = nullptr, *range = nullptr, *cls = nullptr, *open_until = nullptr;
-    size_t keys_cap = 0, skeys_cap = 0, svals_cap = 0, range_cap = 0, cls_cap = 0, open_cap = 0;
-    uint32_t* csort = nullptr;  // the counting pass's per-tile key counts
-    size_t csort_cap = 0;
-    uint4* rec = nullptr;
-    size_t rec_cap = 0;
-    uint8_t* temp = nullptr;
-    size_t temp_cap = 0;
-    uint4 *scan_sum = nullptr, *scan_post = nullptr;  // the scan walk's per-window scratch (dk_tcp::Params)
-    int* scan_ends = nullptr;
-    uint32_t* scan_idx = nullptr;
-    uint4* scan_rec = nullptr;
-    size_t scan_idx_cap = 0, scan_rec_cap = 0;
-    uint32_t* scan_head = nullptr;
-    size_t scan_sum_cap = 0, scan_post_cap = 0, scan_ends_cap = 0, scan_head_cap = 0;
+    dk::ctl::CallOrder serial;
+    dk::ctl::Buf<uint32_t> keys, skeys, svals, range, cls, open_until;
+    dk::ctl::Buf<uint32_t> csort;  // the counting pass's per-tile key counts
+    dk::ctl::Buf<uint4> rec;
+    dk::ctl::Buf<uint8_t> temp;
+    dk::ctl::Buf<uint4> scan_sum, scan_post;  // the scan walk's per-window scratch (dk_tcp::Params)
+    dk::ctl::Buf<int> scan_ends;
+    dk::ctl::Buf<uint32_t> scan_idx;
+    dk::ctl::Buf<uint4> scan_rec;
+    dk::ctl::Buf<uint32_t> scan_head;
     // the stream's shape (pick_walk): the fix kernel's STORED count of each call, in host-mapped memory
     uint32_t* shape = nullptr;            // device u64 (8-byte aligned: hipMalloc), zero between calls
     volatile uint32_t* shape_host = nullptr;  // host-mapped [3] {STORED, n, call}
@@ -1778,8 +1750,8 @@ struct dk_tcp_ctx {
 
 int dk_tcp_ctx_order(dk_tcp_ctx* t, dk_tcp_order* o) {
     if (!t || !o) return EINVAL;
-    *o = dk_tcp_order{t->device, t->svals, t->range, t->rec, t->ord_live, t->ord_n, t->ord_nconns, t->ord_call,
-                      t->last, &t->last_stream, &t->used, &t->ack, &t->emit, &t->cc};
+    *o = dk_tcp_order{t->device, t->svals.p, t->range.p, t->rec.p, t->ord_live, t->ord_n, t->ord_nconns, t->ord_call,
+                      &t->serial, &t->ack, &t->emit, &t->cc};
     return 0;
 }
 
@@ -1794,7 +1766,7 @@ int dk_tcp_ctx_create(int32_t device, dk_tcp_ctx** out) {
     dk_tcp_ctx* t = new dk_tcp_ctx();
     t->device = device;
     void* hs = nullptr;
-    if (hipEventCreateWithFlags(&t->last, hipEventDisableTiming) != hipSuccess) {
+    if (hipEventCreateWithFlags(&t->serial.last, hipEventDisableTiming) != hipSuccess) {
         delete t;
         return EINVAL;
     }
@@ -1803,7 +1775,7 @@ int dk_tcp_ctx_create(int32_t device, dk_tcp_ctx** out) {
         hipHostGetDevicePointer(reinterpret_cast<void**>(&t->shape_host_dev), hs, 0) != hipSuccess) {
         if (hs) (void)hipHostFree(hs);
         if (t->shape) (void)hipFree(t->shape);
-        (void)hipEventDestroy(t->last);
+        (void)hipEventDestroy(t->serial.last);
         delete t;
         return ENOMEM;
     }
@@ -1833,14 +1805,13 @@ int dk_diag_tcp_set_sort(dk_tcp_ctx* t, int32_t sort) {
 void dk_tcp_ctx_destroy(dk_tcp_ctx* t) {
     if (!t) return;
     dk_tcp::DeviceGuard g(t->device);
-    if (t->used) (void)hipEventSynchronize(t->last);
-    for (void* p : {(void*)t->keys, (void*)t->skeys, (void*)t->svals, (void*)t->range, (void*)t->rec, (void*)t->temp,
-                    (void*)t->cls, (void*)t->open_until, (void*)t->scan_sum, (void*)t->scan_post, (void*)t->scan_ends,
-                    (void*)t->scan_idx, (void*)t->scan_rec,
-                    (void*)t->scan_head, (void*)t->shape, (void*)t->csort, t->ack.scratch, t->emit.scratch})
-        if (p) (void)hipFree(p);
+    (void)t->serial.drain();
+    dk::ctl::free_all(t->keys, t->skeys, t->svals, t->range, t->rec, t->temp, t->cls, t->open_until, t->scan_sum,
+                      t->scan_post, t->scan_ends, t->scan_idx, t->scan_rec, t->scan_head, t->csort, t->ack.scratch,
+                      t->emit.scratch);
+    if (t->shape) (void)hipFree(t->shape);
     if (t->shape_host) (void)hipHostFree(const_cast<uint32_t*>(t->shape_host));
-    (void)hipEventDestroy(t->last);
+    (void)hipEventDestroy(t->serial.last);
     delete t;
 }
 
@@ -1863,16 +1834,14 @@ int dk_tcp_rx_process(dk_tcp_ctx* t, const dk_rx_results* rx, uint32_t n, dk_tcp
     }
     DeviceGuard g(t->device);
     const hipStream_t s = (hipStream_t)stream;
+    dk::ctl::CallOrder& o = t->serial;
+    // a HIP failure is EINVAL here (dk_tcp.h); ENOMEM stays
+    const auto grown = [](int rc) { return rc == EIO ? EINVAL : rc; };
     int rc = 0;
-    if (t->used && t->last_stream != s && hipStreamWaitEvent(s, t->last, 0) != hipSuccess) return EINVAL;
-    const bool grows = t->keys_cap < n || t->rec_cap < n || t->range_cap < 2 * (size_t)nconns + 1 || t->cls_cap < n ||
-                       t->open_cap < nconns;
-    if (t->used && grows && hipEventSynchronize(t->last) != hipSuccess) return EINVAL;  // in-flight work on the scratch
-    if ((rc = grow(t->keys, t->keys_cap, n)) || (rc = grow(t->skeys, t->skeys_cap, n)) ||
-        (rc = grow(t->svals, t->svals_cap, n)) || (rc = grow(t->rec, t->rec_cap, n)) ||
-        (rc = grow(t->range, t->range_cap, 2 * (size_t)nconns + 1)) || (rc = grow(t->cls, t->cls_cap, n)) ||
-        (rc = grow(t->open_until, t->open_cap, nconns)))
-        return rc;
+    if (o.order(s)) return EINVAL;
+    if ((rc = t->keys.grow(o, n)) || (rc = t->skeys.grow(o, n)) || (rc = t->svals.grow(o, n)) || (rc = t->rec.grow(o, n)) ||
+        (rc = t->range.grow(o, 2 * (size_t)nconns + 1)) || (rc = t->cls.grow(o, n)) || (rc = t->open_until.grow(o, nconns)))
+        return grown(rc);
     // The shape of the stream from the last call whose fix kernel has completed (never waited for: a call still in
     // flight leaves the previous reading in place).
     if (t->calls != t->seen && t->shape_host[2] != t->seen) {
@@ -1887,16 +1856,10 @@ int dk_tcp_rx_process(dk_tcp_ctx* t, const dk_rx_results* rx, uint32_t n, dk_tcp
     t->last_walk = (int)walker;
     if (walker == dk_tcp::kScanWalk) {  // windows: ws = range[2c] / 64 + c + v < n / 64 + nconns + 1
         const size_t nw = (size_t)n / 64 + nconns + 1;
-        if (t->used &&
-            (t->scan_sum_cap < dk_tcp::kScanSum * nw || t->scan_ends_cap < nw * 64 || t->scan_head_cap < 8ull * nconns ||
-             t->scan_idx_cap < nw * 64 || t->scan_rec_cap < nw * 64) &&
-            hipEventSynchronize(t->last) != hipSuccess)
-            return EINVAL;
-        if ((rc = grow(t->scan_sum, t->scan_sum_cap, dk_tcp::kScanSum * nw)) || (rc = grow(t->scan_post, t->scan_post_cap, nw)) ||
-            (rc = grow(t->scan_ends, t->scan_ends_cap, nw * 64)) || (rc = grow(t->scan_idx, t->scan_idx_cap, nw * 64)) ||
-            (rc = grow(t->scan_rec, t->scan_rec_cap, nw * 64)) ||
-            (rc = grow(t->scan_head, t->scan_head_cap, 8 * (size_t)nconns)))
-            return rc;
+        if ((rc = t->scan_sum.grow(o, dk_tcp::kScanSum * nw)) || (rc = t->scan_post.grow(o, nw)) ||
+            (rc = t->scan_ends.grow(o, nw * 64)) || (rc = t->scan_idx.grow(o, nw * 64)) ||
+            (rc = t->scan_rec.grow(o, nw * 64)) || (rc = t->scan_head.grow(o, 8 * (size_t)nconns)))
+            return grown(rc);
     }
     int bits = 1;
     while (bits < 32 && (1ull << bits) <= 2ull * nconns) bits++;  // keys are 0 .. 2 nconns
@@ -1908,15 +1871,13 @@ int dk_tcp_rx_process(dk_tcp_ctx* t, const dk_rx_results* rx, uint32_t n, dk_tcp
     t->last_sort = nconns && n ? (csort ? 0 : 1) : -1;
     if (csort) {
         const size_t hb = (size_t)nkeys * ntiles;
-        if (t->used && t->csort_cap < hb && hipEventSynchronize(t->last) != hipSuccess) return EINVAL;
-        if ((rc = grow(t->csort, t->csort_cap, hb))) return rc;
+        if ((rc = t->csort.grow(o, hb))) return grown(rc);
     } else {
         size_t sort_bytes = 0;
-        if (rocprim::radix_sort_pairs<SortConfig>(nullptr, sort_bytes, t->keys, t->skeys, index, t->svals, n, 0, bits,
+        if (rocprim::radix_sort_pairs<SortConfig>(nullptr, sort_bytes, t->keys.p, t->skeys.p, index, t->svals.p, n, 0, bits,
                                                   s) != hipSuccess)
             return EINVAL;
-        if (t->used && t->temp_cap < sort_bytes && hipEventSynchronize(t->last) != hipSuccess) return EINVAL;
-        if ((rc = grow(t->temp, t->temp_cap, sort_bytes))) return rc;
+        if ((rc = t->temp.grow(o, sort_bytes))) return grown(rc);
     }
 
     Params P{};
@@ -1928,19 +1889,19 @@ int dk_tcp_rx_process(dk_tcp_ctx* t, const dk_rx_results* rx, uint32_t n, dk_tcp
     P.n = n;
     P.conns = conns;
     P.nconns = nconns;
-    P.keys = t->keys;
-    P.skeys = t->skeys;
-    P.svals = t->svals;
-    P.rec = t->rec;
-    P.range = t->range;
-    P.cls = t->cls;
-    P.open_until = t->open_until;
-    P.scan_sum = t->scan_sum;
-    P.scan_post = t->scan_post;
-    P.scan_ends = t->scan_ends;
-    P.scan_idx = t->scan_idx;
-    P.scan_rec = t->scan_rec;
-    P.scan_head = t->scan_head;
+    P.keys = t->keys.p;
+    P.skeys = t->skeys.p;
+    P.svals = t->svals.p;
+    P.rec = t->rec.p;
+    P.range = t->range.p;
+    P.cls = t->cls.p;
+    P.open_until = t->open_until.p;
+    P.scan_sum = t->scan_sum.p;
+    P.scan_post = t->scan_post.p;
+    P.scan_ends = t->scan_ends.p;
+    P.scan_idx = t->scan_idx.p;
+    P.scan_rec = t->scan_rec.p;
+    P.scan_head = t->scan_head.p;
     P.shape = t->shape;
     P.shape_host = t->shape_host_dev;
     P.call = t->calls + 1;
@@ -1956,11 +1917,11 @@ int dk_tcp_rx_process(dk_tcp_ctx* t, const dk_rx_results* rx, uint32_t n, dk_tcp
         };
         uint32_t mask = 1;  // the key's bits: 2^bits - 1 >= nkeys - 1
         while (mask < nkeys - 1) mask = 2 * mask + 1;
-        pass(SortPass{t->keys, nullptr, nullptr, t->svals, t->csort, 0u, mask, nkeys}, t->range);
+        pass(SortPass{t->keys.p, nullptr, nullptr, t->svals.p, t->csort.p, 0u, mask, nkeys}, t->range.p);
     } else {
         if (n) {
-            size_t b = t->temp_cap;
-            if (rocprim::radix_sort_pairs<SortConfig>(t->temp, b, t->keys, t->skeys, index, t->svals, n, 0, bits, s) !=
+            size_t b = t->temp.cap;
+            if (rocprim::radix_sort_pairs<SortConfig>(t->temp.p, b, t->keys.p, t->skeys.p, index, t->svals.p, n, 0, bits, s) !=
                 hipSuccess)
                 return EINVAL;
         }
@@ -1998,10 +1959,7 @@ int dk_tcp_rx_process(dk_tcp_ctx* t, const dk_rx_results* rx, uint32_t n, dk_tcp
         hipLaunchKernelGGL(dk_tcp_fix_kernel, gn, dim3(kBlock), 0, s, P);
         t->calls++;
     }
-    if (hipGetLastError() != hipSuccess) return EINVAL;
-    if (hipEventRecord(t->last, s) != hipSuccess) return EINVAL;
-    t->last_stream = s;
-    t->used = true;
+    if (o.record(s)) return EINVAL;
     t->ord_live = true, t->ord_n = n, t->ord_nconns = nconns, t->ord_call++;
     return 0;
 }

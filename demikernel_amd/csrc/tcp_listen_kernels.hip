@@ -572,10 +572,10 @@ int dk_tcp_listen_table_create(int32_t device, uint32_t cap, dk_tcp_listen_table
 void dk_tcp_listen_table_destroy(dk_tcp_listen_table* t) {
     if (!t) return;
     dk::ctl::DeviceGuard g(t->device);
-    if (t->call.used) (void)hipEventSynchronize(t->call.last);
+    (void)t->call.drain();
     if (t->slots) (void)hipFree(t->slots);
     if (t->consumed) (void)hipFree(t->consumed);
-    if (t->call.scratch) (void)hipFree(t->call.scratch);
+    t->call.scratch.free();
     if (t->call.last) (void)hipEventDestroy(t->call.last);
     delete t;
 }
@@ -585,7 +585,7 @@ int dk_tcp_listen_table_stats(dk_tcp_listen_table* t, uint32_t* cap, uint64_t* c
     dk::ctl::DeviceGuard g(t->device);
     if (cap) *cap = t->cap;
     if (consumed) {
-        if (t->call.used && hipEventSynchronize(t->call.last) != hipSuccess) return EIO;
+        if (t->call.drain()) return EIO;
         if (hipMemcpy(consumed, t->consumed, sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess) return EIO;
     }
     return 0;
@@ -594,7 +594,7 @@ int dk_tcp_listen_table_stats(dk_tcp_listen_table* t, uint32_t* cap, uint64_t* c
 int dk_tcp_listen_table_read(dk_tcp_listen_table* t, dk_tcp_lsn_slot* rows) {
     if (!t || !rows) return EINVAL;
     dk::ctl::DeviceGuard g(t->device);
-    if (t->call.used && hipEventSynchronize(t->call.last) != hipSuccess) return EIO;
+    if (t->call.drain()) return EIO;
     return hipMemcpy(rows, t->slots, (size_t)t->cap * sizeof(dk_tcp_lsn_slot), hipMemcpyDeviceToHost) == hipSuccess ? 0
                                                                                                                      : EIO;
 }
@@ -602,7 +602,7 @@ int dk_tcp_listen_table_read(dk_tcp_listen_table* t, dk_tcp_lsn_slot* rows) {
 int dk_tcp_listen_table_write(dk_tcp_listen_table* t, const dk_tcp_lsn_slot* rows) {
     if (!t || !rows) return EINVAL;
     dk::ctl::DeviceGuard g(t->device);
-    if (t->call.used && hipEventSynchronize(t->call.last) != hipSuccess) return EIO;
+    if (t->call.drain()) return EIO;
     uint64_t consumed = 0;
     for (uint32_t s = 0; s < t->cap; s++) consumed += rows[s].state != DK_TCP_LSN_FREE;
     if (hipMemcpy(t->slots, rows, (size_t)t->cap * sizeof(dk_tcp_lsn_slot), hipMemcpyHostToDevice) != hipSuccess ||
@@ -649,7 +649,7 @@ int dk_tcp_listen_process(dk_tcp_listen_table* t, const dk_rx_results* rx, uint3
     P.out = out, P.out_bytes = out_bytes, P.stride = layout->slot_stride, P.lead = layout->frame_lead;
     P.max_frames = max_frames, P.max_ready = max_ready, P.flags = flags, P.res = *res;
     P.H = H, P.tile = tile, P.ntiles = ntiles;
-    Carver c{static_cast<uint8_t*>(t->call.scratch)};
+    Carver c{t->call.scratch.p};
     uint8_t* ff = c.b;
     P.gkey = c.take<uint64_t>(H);
     P.gfirst = c.take<uint32_t>(H);
@@ -717,7 +717,7 @@ int dk_tcp_listen_timers(dk_tcp_listen_table* t, const dk_tcp_listener* listener
     P.links = links, P.nlinks = nlinks, P.now = now_ns;
     P.out = out, P.out_bytes = out_bytes, P.stride = layout->slot_stride, P.lead = layout->frame_lead;
     P.max_frames = max_frames, P.max_ready = max_ready, P.flags = flags, P.res = *res;
-    Carver c{static_cast<uint8_t*>(t->call.scratch)};
+    Carver c{t->call.scratch.p};
     uint8_t* zz = c.b;
     P.lwork = c.take<uint32_t>(nl);
     P.tot = c.take<uint64_t>(2);

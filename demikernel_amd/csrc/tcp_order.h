@@ -1,7 +1,9 @@
-// tcp_order.h — what a dk_tcp_rx_process call leaves in its context for the call that follows it on the same batch
+// tcp_order.h — what the calls on the two TCP data-plane contexts that live in other files than their context need of
+// it. Of a dk_tcp_ctx (tcp_kernels.hip), for the calls that follow a dk_tcp_rx_process call on the same batch
 // (dk_tcp_ack_process, tcp_ack_kernels.hip; dk_tcp_ack_emit, tcp_ackemit_kernels.hip; dk_tcp_cc_ack,
-// tcp_cc_kernels.hip): the batch's order by connection, still in the context's scratch, and the
-// context's serialisation state. Internal to libdk_rx.so.
+// tcp_cc_kernels.hip): the batch's order by connection, still in the context's buffers, the followers' own state, and
+// the context's call order. Of a dk_tcp_tx_ctx (tcp_tx_kernels.hip): its call order and dk_tcp_tx_commit's state. The
+// call order and the buffers are ctl_common.h's CallOrder and Buf. Internal to libdk_rx.so.
 #ifndef DK_TCP_ORDER_H
 #define DK_TCP_ORDER_H
 
@@ -9,14 +11,15 @@
 
 #include <cstdint>
 
+#include "ctl_common.h"
+
 struct dk_tcp_ctx;
 
 struct dk_tcp_ack_state {
     int form = -1;       // dk_diag_tcp_ack_set_form: 0 lane, 1 wave, 2 chip, -1 the rule
     int last_form = -1;  // the form the last dk_tcp_ack_process call ran
     uint32_t done = 0;   // the dk_tcp_rx_process call number the last dk_tcp_ack_process call consumed
-    void* scratch = nullptr;  // the chip form's per-window arrays (device; freed by dk_tcp_ctx_destroy)
-    size_t scratch_cap = 0;
+    dk::ctl::Buf<uint8_t> scratch;  // the chip form's per-window arrays (freed by dk_tcp_ctx_destroy)
 };
 
 // dk_tcp_ack_emit's own turn counter and scratch (freed by dk_tcp_ctx_destroy): it and dk_tcp_ack_process may both
@@ -25,8 +28,7 @@ struct dk_tcp_emit_state {
     int form = -1;       // dk_diag_tcp_ack_emit_set_form: 0 lane, 1 wave, -1 the rule
     int last_form = -1;  // the form the last dk_tcp_ack_emit call ran
     uint32_t done = 0;   // the dk_tcp_rx_process call number the last dk_tcp_ack_emit call consumed
-    void* scratch = nullptr;
-    size_t scratch_cap = 0;
+    dk::ctl::Buf<uint8_t> scratch;
 };
 
 // dk_tcp_cc_ack's turn counter (tcp_cc_kernels.hip): it follows a dk_tcp_rx_process call as the two above do, once, and
@@ -46,9 +48,7 @@ struct dk_tcp_order {
     bool live;              // the last dk_tcp_rx_process call completed its launches: the three arrays are its
     uint32_t n, nconns;     // that call's
     uint32_t call;          // its number on this context (from 1)
-    hipEvent_t last;        // the context's serialisation (tcp_kernels.hip, struct dk_tcp_ctx)
-    hipStream_t* last_stream;
-    bool* used;
+    dk::ctl::CallOrder* serial;  // the context's call order (tcp_kernels.hip, struct dk_tcp_ctx)
     dk_tcp_ack_state* ack;
     dk_tcp_emit_state* emit;
     dk_tcp_cc_state* cc;
@@ -65,19 +65,16 @@ struct dk_tcp_commit_state {
     uint32_t seg_call = 0;   // the dk_tcp_tx_segment calls of this context that returned 0
     uint32_t seg_nbufs = 0;  // the last one's nbufs
     uint32_t done = 0;       // the dk_tcp_tx_segment call number the last dk_tcp_tx_commit call consumed
-    void* scratch = nullptr;
-    size_t scratch_cap = 0;
+    dk::ctl::Buf<uint2> scratch;
 };
 
-// The serialisation state of a dk_tcp_tx_ctx (tcp_tx_kernels.hip), for the calls on it that live in other files
+// The call order of a dk_tcp_tx_ctx (tcp_tx_kernels.hip), for the calls on it that live in other files
 // (dk_tcp_timers, dk_tcp_cc_send: tcp_cc_kernels.hip; dk_tcp_tx_commit, dk_tcp_rtx_piggyback: tcp_commit_kernels.hip).
 // Only dk_tcp_tx_commit uses scratch of the context, its own.
 struct dk_tcp_tx_ctx;
 struct dk_tcp_tx_serial {
     int device;
-    hipEvent_t last;
-    hipStream_t* last_stream;
-    bool* used;
+    dk::ctl::CallOrder* serial;
     uint32_t cus;
     dk_tcp_commit_state* commit;
 };

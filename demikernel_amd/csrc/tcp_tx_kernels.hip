@@ -368,27 +368,7 @@ __global__ __launch_bounds__(kBlock) void ack_timer_commit(AckTimerPlan P) {
     P.dack[c].armed = 0;  // emit() clears the deadline (ctrlblk.rs:761); deadline_ns is left as it is
 }
 
-struct DeviceGuard {
-    int prev = -1;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) (void)hipSetDevice(dev);
-    }
-    ~DeviceGuard() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
-template <class T>
-int grow(T*& p, size_t& cap, size_t n) {
-    if (cap >= n) return 0;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    if (hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess) return ENOMEM;
-    cap = n;
-    return 0;
-}
+using dk::ctl::DeviceGuard;
 
 std::atomic<int32_t> g_emit_grid{-1};  // dk_diag_tcp_tx_set_grid
 
@@ -408,31 +388,24 @@ int scan(uint64_t* a0, uint64_t* a1, uint32_t n, uint64_t* bsum, uint32_t nb, ui
 // previous one first waits, on the device, for the previous call's work).
 struct dk_tcp_tx_ctx {
     int device = 0;
-    hipEvent_t last = nullptr;
-    hipStream_t last_stream = nullptr;
-    bool used = false;
+    dk::ctl::CallOrder serial;
     uint32_t cus = 0, occ = 0;
-    uint64_t *seqsp = nullptr, *flags = nullptr, *frames = nullptr, *bsum = nullptr, *tot = nullptr;
-    size_t seqsp_cap = 0, flags_cap = 0, frames_cap = 0, bsum_cap = 0, tot_cap = 0;
-    uint32_t *head = nullptr, *tail = nullptr;
-    size_t head_cap = 0, tail_cap = 0;
-    uint4* rec = nullptr;
-    uint2* cm = nullptr;
-    size_t rec_cap = 0, cm_cap = 0;
+    dk::ctl::Buf<uint64_t> seqsp, flags, frames, bsum, tot;
+    dk::ctl::Buf<uint32_t> head, tail;
+    dk::ctl::Buf<uint4> rec;
+    dk::ctl::Buf<uint2> cm;
     // dk_tcp_retransmit's: the emit flags / their scan and the records per connection (tot[3] is its total)
-    uint64_t* rtx_emit = nullptr;
-    uint4* rtx_rec = nullptr;
-    size_t rtx_emit_cap = 0, rtx_rec_cap = 0;
+    dk::ctl::Buf<uint64_t> rtx_emit;
+    dk::ctl::Buf<uint4> rtx_rec;
     // dk_tcp_ack_timer's emit flags / their scan per connection (tot[4] is its total)
-    uint64_t* ackt_emit = nullptr;
-    size_t ackt_emit_cap = 0;
+    dk::ctl::Buf<uint64_t> ackt_emit;
     // dk_tcp_tx_commit's turn after dk_tcp_tx_segment, its form and its scratch (tcp_commit_kernels.hip)
     dk_tcp_commit_state commit;
 };
 
 int dk_tcp_tx_ctx_serial(dk_tcp_tx_ctx* t, dk_tcp_tx_serial* o) {
     if (!t || !o) return EINVAL;
-    *o = dk_tcp_tx_serial{t->device, t->last, &t->last_stream, &t->used, t->cus, &t->commit};
+    *o = dk_tcp_tx_serial{t->device, &t->serial, t->cus, &t->commit};
     return 0;
 }
 
@@ -462,12 +435,12 @@ int dk_tcp_tx_ctx_create(int32_t device, dk_tcp_tx_ctx** out) {
     t->device = device;
     t->cus = (uint32_t)cus;
     t->occ = (uint32_t)std::max(dk_tcp_tx_emit_resident_blocks(), 1);
-    if (hipEventCreateWithFlags(&t->last, hipEventDisableTiming) != hipSuccess) {
+    if (hipEventCreateWithFlags(&t->serial.last, hipEventDisableTiming) != hipSuccess) {
         delete t;
         return EINVAL;
     }
-    if (dk_tcp_tx::grow(t->tot, t->tot_cap, 5)) {
-        (void)hipEventDestroy(t->last);
+    if (t->tot.grow(t->serial, 5)) {
+        (void)hipEventDestroy(t->serial.last);
         delete t;
         return ENOMEM;
     }
@@ -478,12 +451,10 @@ int dk_tcp_tx_ctx_create(int32_t device, dk_tcp_tx_ctx** out) {
 void dk_tcp_tx_ctx_destroy(dk_tcp_tx_ctx* t) {
     if (!t) return;
     dk_tcp_tx::DeviceGuard g(t->device);
-    if (t->used) (void)hipEventSynchronize(t->last);
-    for (void* p : {(void*)t->seqsp, (void*)t->flags, (void*)t->frames, (void*)t->bsum, (void*)t->tot, (void*)t->head,
-                    (void*)t->tail, (void*)t->rec, (void*)t->cm, (void*)t->rtx_emit, (void*)t->rtx_rec,
-                    (void*)t->ackt_emit, t->commit.scratch})
-        if (p) (void)hipFree(p);
-    (void)hipEventDestroy(t->last);
+    (void)t->serial.drain();
+    dk::ctl::free_all(t->seqsp, t->flags, t->frames, t->bsum, t->tot, t->head, t->tail, t->rec, t->cm, t->rtx_emit,
+                      t->rtx_rec, t->ackt_emit, t->commit.scratch);
+    (void)hipEventDestroy(t->serial.last);
     delete t;
 }
 
@@ -509,30 +480,28 @@ int dk_tcp_tx_segment(dk_tcp_tx_ctx* t, const uint8_t* src, uint64_t src_bytes, 
     if (nbufs && max_frames && (!out || !res->off_out || !res->len_out)) return EINVAL;
     DeviceGuard g(t->device);
     const hipStream_t s = (hipStream_t)stream;
-    if (t->used && t->last_stream != s && hipStreamWaitEvent(s, t->last, 0) != hipSuccess) return EIO;
+    if (t->serial.order(s)) return EIO;
     if (nbufs == 0) {
         if (hipMemsetAsync(res->n_frames, 0, sizeof(uint32_t), s) != hipSuccess) return EIO;
     } else {
         const uint32_t nb = (nbufs + kTile - 1) / kTile;
-        const bool grows = t->seqsp_cap < nbufs || t->bsum_cap < 2 * (size_t)nb || t->head_cap < nconns;
-        if (t->used && grows && hipEventSynchronize(t->last) != hipSuccess) return EIO;  // in-flight work on the scratch
+        dk::ctl::CallOrder& o = t->serial;
         int rc = 0;
-        if ((rc = grow(t->seqsp, t->seqsp_cap, nbufs)) || (rc = grow(t->flags, t->flags_cap, nbufs)) ||
-            (rc = grow(t->frames, t->frames_cap, nbufs)) || (rc = grow(t->bsum, t->bsum_cap, 2 * (size_t)nb)) ||
-            (rc = grow(t->head, t->head_cap, nconns)) || (rc = grow(t->tail, t->tail_cap, nconns)) ||
-            (rc = grow(t->rec, t->rec_cap, nbufs)) || (rc = grow(t->cm, t->cm_cap, nbufs)))
+        if ((rc = t->seqsp.grow(o, nbufs)) || (rc = t->flags.grow(o, nbufs)) || (rc = t->frames.grow(o, nbufs)) ||
+            (rc = t->bsum.grow(o, 2 * (size_t)nb)) || (rc = t->head.grow(o, nconns)) || (rc = t->tail.grow(o, nconns)) ||
+            (rc = t->rec.grow(o, nbufs)) || (rc = t->cm.grow(o, nbufs)))
             return rc;
         Plan P{src, src_bytes, out_bytes, push->conn, push->off, push->len, nbufs, tx_conns, rx_conns, nconns, nlinks,
-               layout->slot_stride, layout->frame_lead, max_frames, t->seqsp, t->flags, t->frames, t->tot, t->head,
-               t->tail, t->rec, t->cm, *res};
+               layout->slot_stride, layout->frame_lead, max_frames, t->seqsp.p, t->flags.p, t->frames.p, t->tot.p,
+               t->head.p, t->tail.p, t->rec.p, t->cm.p, *res};
         const dim3 per_buf((nbufs + kBlock - 1) / kBlock);
         hipLaunchKernelGGL(fill_kernel, per_buf, dim3(kBlock), 0, s, P);
-        if ((rc = scan(t->seqsp, t->flags, nbufs, t->bsum, nb, t->tot + 0, t->tot + 1, s))) return rc;
+        if ((rc = scan(t->seqsp.p, t->flags.p, nbufs, t->bsum.p, nb, t->tot.p + 0, t->tot.p + 1, s))) return rc;
         hipLaunchKernelGGL(plan_kernel, per_buf, dim3(kBlock), 0, s, P);
-        if ((rc = scan(t->frames, nullptr, nbufs, t->bsum, nb, t->tot + 2, nullptr, s))) return rc;
+        if ((rc = scan(t->frames.p, nullptr, nbufs, t->bsum.p, nb, t->tot.p + 2, nullptr, s))) return rc;
         // emit reads the connections the commit updates (never snd_nxt or fin_sent), and runs first
-        dk::TcpTxEmitParams E{src, out, out_bytes, push->conn, push->off, push->len, nbufs, tx_conns, links, t->frames,
-                              t->tot + 2, reinterpret_cast<const uint32_t*>(t->rec), layout->slot_stride,
+        dk::TcpTxEmitParams E{src, out, out_bytes, push->conn, push->off, push->len, nbufs, tx_conns, links, t->frames.p,
+                              t->tot.p + 2, reinterpret_cast<const uint32_t*>(t->rec.p), layout->slot_stride,
                               layout->frame_lead, max_frames, flags, res->off_out, res->len_out, res->frame_buf};
         // the persistent grid is sized from what the host knows: the frames the outputs have room for
         // (a workgroup's four waves take 256 frames a round)
@@ -541,11 +510,8 @@ int dk_tcp_tx_segment(dk_tcp_tx_ctx* t, const uint8_t* src, uint64_t src_bytes, 
         if (cap > 0) grid = std::min(grid, (uint32_t)cap);
         if (max_frames && (rc = dk_launch_tcp_tx_emit(E, grid, s))) return EIO;
         hipLaunchKernelGGL(commit_kernel, per_buf, dim3(kBlock), 0, s, P);
-        if (hipGetLastError() != hipSuccess) return EIO;
     }
-    if (hipEventRecord(t->last, s) != hipSuccess) return EIO;
-    t->last_stream = s;
-    t->used = true;
+    if (t->serial.record(s)) return EIO;
     if (++t->commit.seg_call == 0) t->commit.seg_call = 1;  // dk_tcp_tx_commit's turn; 0 stays "no call yet"
     t->commit.seg_nbufs = nbufs;
     return 0;
@@ -569,36 +535,30 @@ int dk_tcp_retransmit(dk_tcp_tx_ctx* t, const uint8_t* src, uint64_t src_bytes, 
     if (nconns && max_frames && (!out || !res->off_out || !res->len_out)) return EINVAL;
     DeviceGuard g(t->device);
     const hipStream_t s = (hipStream_t)stream;
-    if (t->used && t->last_stream != s && hipStreamWaitEvent(s, t->last, 0) != hipSuccess) return EIO;
+    if (t->serial.order(s)) return EIO;
     if (nconns == 0) {
         if (hipMemsetAsync(res->n_frames, 0, sizeof(uint32_t), s) != hipSuccess) return EIO;
     } else {
         const uint32_t nb = (nconns + kTile - 1) / kTile;
-        const bool grows = t->rtx_emit_cap < nconns || t->rtx_rec_cap < nconns || t->bsum_cap < nb;
-        if (t->used && grows && hipEventSynchronize(t->last) != hipSuccess) return EIO;  // in-flight work on the scratch
         int rc = 0;
-        if ((rc = grow(t->rtx_emit, t->rtx_emit_cap, nconns)) || (rc = grow(t->rtx_rec, t->rtx_rec_cap, nconns)) ||
-            (rc = grow(t->bsum, t->bsum_cap, nb)))
+        if ((rc = t->rtx_emit.grow(t->serial, nconns)) || (rc = t->rtx_rec.grow(t->serial, nconns)) ||
+            (rc = t->bsum.grow(t->serial, nb)))
             return rc;
         RtxPlan P{src_bytes, out_bytes, now_ns, fire, tx_conns, ack_conns, rx_conns, *q, nconns, nq, nlinks,
-                  layout->slot_stride, layout->frame_lead, max_frames, t->rtx_emit, t->tot + 3, t->rtx_rec, *res};
+                  layout->slot_stride, layout->frame_lead, max_frames, t->rtx_emit.p, t->tot.p + 3, t->rtx_rec.p, *res};
         const dim3 per_conn((nconns + kBlock - 1) / kBlock);
         hipLaunchKernelGGL(rtx_plan, per_conn, dim3(kBlock), 0, s, P);
-        if ((rc = scan(t->rtx_emit, nullptr, nconns, t->bsum, nb, t->tot + 3, nullptr, s))) return rc;
+        if ((rc = scan(t->rtx_emit.p, nullptr, nconns, t->bsum.p, nb, t->tot.p + 3, nullptr, s))) return rc;
         // emit reads the records, never the rows the commit writes, and runs first
-        dk::TcpRtxEmitParams E{src, out, out_bytes, tx_conns, links, t->rtx_emit, t->tot + 3,
-                               reinterpret_cast<const uint32_t*>(t->rtx_rec), nconns, layout->slot_stride,
+        dk::TcpRtxEmitParams E{src, out, out_bytes, tx_conns, links, t->rtx_emit.p, t->tot.p + 3,
+                               reinterpret_cast<const uint32_t*>(t->rtx_rec.p), nconns, layout->slot_stride,
                                layout->frame_lead, max_frames, flags, res->off_out, res->len_out, res->frame_conn};
         // sized from what the host knows: a frame per connection at most, and no more than the outputs have room for
         const uint32_t grid = std::min<uint32_t>(std::min(max_frames, nconns) / 256 + 1, std::min(t->occ, 8u) * t->cus);
         if (max_frames && dk_launch_tcp_rtx_emit(E, grid, s)) return EIO;
         hipLaunchKernelGGL(rtx_commit, per_conn, dim3(kBlock), 0, s, P);
-        if (hipGetLastError() != hipSuccess) return EIO;
     }
-    if (hipEventRecord(t->last, s) != hipSuccess) return EIO;
-    t->last_stream = s;
-    t->used = true;
-    return 0;
+    return t->serial.record(s);
 }
 
 int dk_tcp_ack_timer(dk_tcp_tx_ctx* t, const uint8_t* fire, const dk_tcp_tx_conn* tx_conns, const dk_tcp_conn* rx_conns,
@@ -616,33 +576,27 @@ int dk_tcp_ack_timer(dk_tcp_tx_ctx* t, const uint8_t* fire, const dk_tcp_tx_conn
     if (nconns && max_frames && (!out || !res->off_out || !res->len_out)) return EINVAL;
     DeviceGuard g(t->device);
     const hipStream_t s = (hipStream_t)stream;
-    if (t->used && t->last_stream != s && hipStreamWaitEvent(s, t->last, 0) != hipSuccess) return EIO;
+    if (t->serial.order(s)) return EIO;
     if (nconns == 0) {
         if (hipMemsetAsync(res->n_frames, 0, sizeof(uint32_t), s) != hipSuccess) return EIO;
     } else {
         const uint32_t nb = (nconns + kTile - 1) / kTile;
-        const bool grows = t->ackt_emit_cap < nconns || t->bsum_cap < nb;
-        if (t->used && grows && hipEventSynchronize(t->last) != hipSuccess) return EIO;  // in-flight work on the scratch
         int rc = 0;
-        if ((rc = grow(t->ackt_emit, t->ackt_emit_cap, nconns)) || (rc = grow(t->bsum, t->bsum_cap, nb))) return rc;
+        if ((rc = t->ackt_emit.grow(t->serial, nconns)) || (rc = t->bsum.grow(t->serial, nb))) return rc;
         AckTimerPlan P{out_bytes, fire, tx_conns, rx_conns, dack, nconns, nlinks, layout->slot_stride, layout->frame_lead,
-                       max_frames, t->ackt_emit, t->tot + 4, *res};
+                       max_frames, t->ackt_emit.p, t->tot.p + 4, *res};
         const dim3 per_conn((nconns + kBlock - 1) / kBlock);
         hipLaunchKernelGGL(ack_timer_plan, per_conn, dim3(kBlock), 0, s, P);
-        if ((rc = scan(t->ackt_emit, nullptr, nconns, t->bsum, nb, t->tot + 4, nullptr, s))) return rc;
+        if ((rc = scan(t->ackt_emit.p, nullptr, nconns, t->bsum.p, nb, t->tot.p + 4, nullptr, s))) return rc;
         // emit reads the tables, never the rows the commit writes, and runs first
-        dk::TcpAckEmitParams E{out, out_bytes, tx_conns, rx_conns, links, t->ackt_emit, t->tot + 4, nullptr, nullptr,
+        dk::TcpAckEmitParams E{out, out_bytes, tx_conns, rx_conns, links, t->ackt_emit.p, t->tot.p + 4, nullptr, nullptr,
                                nconns, layout->slot_stride, layout->frame_lead, max_frames, flags, res->off_out,
                                res->len_out, res->frame_conn, nullptr};
         const uint32_t grid = std::min<uint32_t>(std::min(max_frames, nconns) / 256 + 1, 8u * t->cus);
         if (max_frames && dk_launch_tcp_ack_emit(E, grid, s)) return EIO;
         hipLaunchKernelGGL(ack_timer_commit, per_conn, dim3(kBlock), 0, s, P);
-        if (hipGetLastError() != hipSuccess) return EIO;
     }
-    if (hipEventRecord(t->last, s) != hipSuccess) return EIO;
-    t->last_stream = s;
-    t->used = true;
-    return 0;
+    return t->serial.record(s);
 }
 
 }  // extern "C"

@@ -11,6 +11,7 @@ import pytest
 
 import tcp_ack_cases as C
 import tcp_ack_reference as R
+from ctl_calls import delayed, stream_pair
 from demikernel_amd import Config, FrameBatch, RxEngine, synth
 from demikernel_amd import _native as N
 from demikernel_amd.rx import Fail
@@ -337,17 +338,24 @@ def test_call_order():
 
 
 def test_other_stream_is_serialised():
-    """dk_tcp_ack_process on another stream than its dk_tcp_rx_process waits for it on the device."""
+    """dk_tcp_ack_process on another stream than its dk_tcp_rx_process waits for it on the device: the receive call
+    sits behind 100 ms of sleep on its stream and is still pending when the ACK pass has been queued on the other
+    (tests/test_gpu_tcp_ctx_streams.py has the other chains of the context)."""
     import torch
 
     case = case_three(1)
     d = Device(case)
     try:
-        d.receive()
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())  # the tables' uploads; the context's own event orders the rest
-        d.ack("wave", stream=s)
-        s.synchronize()
+        c = d.case
+        d.eng.receive_batch(FrameBatch.from_numpy(c["blob"], c["off"], c["lens"], device=0), d.r)
+        A, B, _ = stream_pair()
+        for s in (A, B):
+            s.wait_stream(torch.cuda.current_stream())  # the uploads and dk_rx_process; the context's event orders the rest
+        ev = delayed(A)
+        d.tcp.process(d.r, d.d_rx, d.out, stream=A)
+        d.ack("wave", stream=B)
+        assert not ev.query(), "the delay ended while the calls were being issued: a call waited on the host"
+        B.synchronize()
         h, act = d.r.to_numpy(), d.out.to_numpy()["action"]
         got = d.read()
         exp = R.ack_process(h["flow_id"], act, h["tcp_seq"], h["tcp_ack"], h["tcp_win"], got["rx_conns"], case["tx"],

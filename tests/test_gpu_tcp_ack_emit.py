@@ -14,6 +14,7 @@ import pytest
 import tcp_ackemit_cases as C
 import tcp_ackemit_reference as E
 import tx_segment_reference as M
+from ctl_calls import delayed, stream_pair
 from demikernel_amd import _native as N
 from demikernel_amd.rx import Fail
 from demikernel_amd.tcp import TcpOut, TcpReceiver
@@ -388,18 +389,29 @@ def test_call_order():
 
 
 def test_other_stream_and_batch_helper():
-    """On another stream than its dk_tcp_rx_process the call waits for it on the device; ack_emit_batch hands the
-    frames on as a FrameBatch."""
+    """On another stream than its dk_tcp_rx_process the call waits for it on the device: the receive call sits behind
+    100 ms of sleep on its stream and is still pending when the ACKs are queued on the other (ack_emit_batch then waits
+    for its stream, so the pending delay is asserted just before it). ack_emit_batch hands the frames on as a
+    FrameBatch."""
     import torch
 
     case = case_total(2049)
     d = Device(case)
     try:
         d.receive()
+        # sizes the call's scratch, so that the call below has nothing to wait for on the host; unchecked. The receive
+        # and the dack tables it moved are uploaded anew below; d_tx is relied on to be unchanged (the call only reads it)
+        d.emit(None)
+        torch.cuda.synchronize()
+        d.d_rx, d.d_dack = d.tcp.conns_to_device(case["table"]), dack_to_device(case["dack"])
         d.d_out = torch.full((case["n"] * 64,), CANARY, dtype=torch.uint8, device=d.d_rx.device)
         d.res = AckEmitResults(case["n"], d.nrows, d.n, fill=FILL)
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())  # the uploads and the fills; the context's own event orders the rest
+        A, s, _ = stream_pair()
+        for x in (A, s):
+            x.wait_stream(torch.cuda.current_stream())  # the uploads and the fills; the context's own event orders the rest
+        ev = delayed(A)
+        d.tcp.process(d.r, d.d_rx, d.out, stream=A)
+        assert not ev.query(), "the delay ended before the ACKs were queued"
         batch = ack_emit_batch(d.tcp, d.r, d.out, d.d_rx, d.d_tx, d.d_dack, d.d_links, NOW, d.d_out, d.res,
                                slot_stride=64, stream=s)
         exp = reference(case, out_size=case["n"] * 64)

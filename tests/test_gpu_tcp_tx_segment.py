@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import tx_segment_reference as M
+from ctl_calls import delayed, stream_pair
 from demikernel_amd import Config, RxEngine, synth
 from demikernel_amd import _native as N
 from demikernel_amd.tcp import TcpOut, TcpReceiver, conn_table
@@ -314,13 +315,17 @@ def test_other_stream_and_back_to_back(sender):
                    state=got["state"])
     assert_same(got2, exp2, src)
     assert list(exp2["status"]) == [M.UNSENT, M.UNSENT, M.SENT]
-    # two calls queued without a wait between them (the second on the current stream: the context orders them)
+    # two calls queued without a wait between them on two streams, the first behind 100 ms of sleep and still pending
+    # when the second has been queued: the context orders them (tests/test_gpu_tcp_ctx_streams.py has the other chains)
     st = got["state"]
     push, r1, r2 = PushList.from_numpy(c, off, ln), TcpTxResults(12, 3), TcpTxResults(12, 3)
     st["tx"].copy_(sender.conns_to_device(tx))
     torch.cuda.synchronize()
-    sender.segment(st["src"], push, st["tx"], st["links"], st["out"], r1, slot_stride=384, stream=s)
-    sender.segment(st["src"], push, st["tx"], st["links"], st["out"], r2, slot_stride=384)
+    A, B, _ = stream_pair()
+    ev = delayed(A)
+    sender.segment(st["src"], push, st["tx"], st["links"], st["out"], r1, slot_stride=384, stream=A)
+    sender.segment(st["src"], push, st["tx"], st["links"], st["out"], r2, slot_stride=384, stream=B)
+    assert not ev.query(), "the delay ended while the calls were being issued: a call waited on the host"
     torch.cuda.synchronize()
     assert np.array_equal(r1.to_numpy()["status"], exp["status"]) and np.array_equal(r2.to_numpy()["status"], exp2["status"])
     assert sender.conns_to_host(st["tx"]).tobytes() == exp2["tx_conns"].tobytes()
