@@ -1,4 +1,5 @@
-// rx_common.h — definitions shared by the host driver (rx_host.cpp) and the HIP kernels (rx_kernels.hip).
+// rx_common.h — definitions shared by the host driver (rx_host.cpp) and the HIP kernels (rx_kernels.hip,
+// tx_build_kernels.hip and the device header they share, frame_build.h).
 #pragma once
 
 #include <stdint.h>
@@ -311,8 +312,8 @@ DK_HD uint32_t tx_tcp_header_bytes(const dk_tcp_opts* o) {
 
 }  // namespace dk
 
-// Launchers implemented in rx_kernels.hip (internal symbols, not part of the C ABI).
-// Receive kernel families (launch_batch picks one per launch).
+// Launchers (internal symbols, not part of the C ABI), by the file that implements them.
+// rx_kernels.hip. Receive kernel families (launch_batch picks one per launch):
 namespace dk {
 constexpr uint32_t kFamilyUnstaged = 0, kFamilyStaged = 1, kFamilySplit = 2, kFamilySmall = 3;
 constexpr uint32_t kFamilySmallUb = 4;  // occupancy queries only: the small-frame kernel with the LDS bind table
@@ -322,12 +323,13 @@ int dk_launch_rx(const dk::RxParams& p, uint32_t grid, void* stream);
 // dk_flow_reduce_kernel over rows left pending by a deferred launch (dk_rx_counts_flush and the scratch paths).
 int dk_launch_reduce(const dk::RowCombine& q, void* stream);
 uint32_t dk_rx_small_block_waves(bool ub);  // waves per workgroup of the small-frame kernel (ub: the LDS bind table's)
-// The host pipeline under the ring's copy policy (rx_host.cpp; dk_rx_process_tpacket3).
-int dk_rx_process_ring_host(struct dk_rx_ctx* c, const dk_rx_batch* b, const dk_rx_results* r);
 int dk_tx_resident_blocks();  // occupancy of dk_tx_kernel per CU (0 on error)
 int dk_launch_tx(const dk::TxParams& p, uint32_t grid, void* stream);
 int dk_tx_serialize_resident_blocks();  // occupancy of dk_tx_serialize_kernel per CU (0 on error)
 int dk_launch_tx_serialize(const dk::TxSerParams& p, uint32_t grid, void* stream);
+// rx_host.cpp: the host pipeline under the ring's copy policy (dk_rx_process_tpacket3).
+int dk_rx_process_ring_host(struct dk_rx_ctx* c, const dk_rx_batch* b, const dk_rx_results* r);
+// tx_build_kernels.hip: the emit passes of dk_tcp_tx_segment, dk_tcp_retransmit and dk_tcp_ack_emit / dk_tcp_ack_timer
 int dk_tcp_tx_emit_resident_blocks();  // occupancy of dk_tcp_tx_emit_kernel per CU (0 on error)
 int dk_launch_tcp_tx_emit(const dk::TcpTxEmitParams& p, uint32_t grid, void* stream);
 int dk_launch_tcp_rtx_emit(const dk::TcpRtxEmitParams& p, uint32_t grid, void* stream);

@@ -1,6 +1,6 @@
 // tcp_ackemit_kernels.hip — the receiver's ACKs on the GPU (include/dk_tcp.h, dk_tcp_ack_emit; dk_tcp_ack_timer's
 // kernels sit with dk_tcp_retransmit's in tcp_tx_kernels.hip, the frame builder both share is dk_tcp_ack_emit_kernel in
-// rx_kernels.hip).
+// tx_build_kernels.hip).
 //
 // ControlBlock::process_packet (ctrlblk.rs:403-440) decides per segment whether an ACK goes out and what becomes of the
 // delayed-ACK deadline; send_ack (:712-720) puts RCV.NXT and the window of that moment into it. dk_tcp_rx_process left

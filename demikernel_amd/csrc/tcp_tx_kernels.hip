@@ -1,6 +1,6 @@
 // tcp_tx_kernels.hip — dk_tcp_tx_segment, dk_tcp_retransmit and dk_tcp_ack_timer (dk_tcp.h): the plan and commit kernels
 // and the host entry points. The emit kernels (the payload copy, the checksums and the headers) are dk_tcp_tx_emit_kernel and
-// dk_tcp_rtx_emit_kernel in rx_kernels.hip, next to the dk_tx_serialize code they share their header arithmetic with.
+// dk_tcp_rtx_emit_kernel in tx_build_kernels.hip; they share their header arithmetic with dk_tx_serialize (frame_build.h).
 //
 // Sender::send_segment (tcp/established/sender.rs:124-208) cuts one segment at a time, each as large as
 // min(send window - in flight, MSS, cwnd - in flight) allows. With no ACK arriving inside a call the windows are fixed,
@@ -13,7 +13,7 @@
 //              to the sum at its head: no segmented scan is needed)
 //   2. plan:   per buffer the connection checks, B, C, take, its frame count, the header's ack and window
 //      scan:   exclusive sum of the frame counts = first_frame, its total = n_frames
-//   3. emit    (rx_kernels.hip), and
+//   3. emit    (tx_build_kernels.hip), and
 //      commit: results per buffer; snd_nxt and fin_sent by the one buffer per connection that knows the total (the
 //              first marker, else the connection's last buffer).
 // Emit and commit both start with the same test of the total against max_frames / out_bytes, so a call that does not
@@ -237,8 +237,8 @@ __global__ __launch_bounds__(kBlock) void commit_kernel(Plan P) {
 }
 
 // dk_tcp_retransmit (dk_tcp.h): one lane per connection plans (the checks in the header's order, emit 0/1, the front
-// entry and the header fields as a record), the scan above numbers the frames, dk_tcp_rtx_emit_kernel (rx_kernels.hip)
-// builds them, and one lane per connection commits behind the same capacity test.
+// entry and the header fields as a record), the scan above numbers the frames, dk_tcp_rtx_emit_kernel
+// (tx_build_kernels.hip) builds them, and one lane per connection commits behind the same capacity test.
 struct RtxPlan {
     uint64_t src_bytes, out_bytes, now_ns;
     const uint8_t* fire;
@@ -323,8 +323,8 @@ __global__ __launch_bounds__(kBlock) void rtx_commit(RtxPlan P) {
 
 // dk_tcp_ack_timer (dk_tcp.h): the acknowledger's expiry, with dk_tcp_retransmit's shape. One lane per connection
 // plans (the checks in the header's order, emit 0/1), the scan numbers the frames, dk_tcp_ack_emit_kernel
-// (rx_kernels.hip) builds them from the tables as they stand, and one lane per connection commits behind the same
-// capacity test.
+// (tx_build_kernels.hip) builds them from the tables as they stand, and one lane per connection commits behind the
+// same capacity test.
 struct AckTimerPlan {
     uint64_t out_bytes;
     const uint8_t* fire;
